@@ -15,13 +15,18 @@ Attempt 1 runs the workers with MAU_DP_GRAPH=1; a worker that exits non-zero or 
 progress is killed (with its process group) and a FRESH set of workers runs the eager step
 (MAU_DP_GRAPH=0) on a fresh rendezvous; should that fail too, a last set runs the eager step with every
 collective through ProcessGroupNCCL (MAU_RCCL_DIRECT=0).  Nothing is ever exec'ed or restarted in place.
-The timed region (exactly K steps between barrier + synchronize) is repeated R times back to back
-(R chosen so the GPU phase lasts >= ~10 s) and the MEDIAN region is reported; the spread is in the line.
+The timed region is exactly K steps between barrier + synchronize: a plain run sets up, warms up, times
+that ONE region and prints its line (--repeats R: R regions back to back, the MEDIAN reported).
 Workload (BASELINE.json configs[1] / configs[3]): U-Net, base_filters 64, 6x256x256 tiles + 4-dim
 metadata, B = 32 per GPU, bf16 MFMA arithmetic with fp32 accumulation, fp32 master weights.
-Prints ONE JSON line on rank 0 (contract in the task description) carrying `roofline` (dominant
-kernel: the 3x3 implicit-GEMM convolution, timed live with events on the launch stream) and
-`cpu_baseline` (the CPU oracle = port of the reference's torch operators, timed on the host cores).
+Prints ONE JSON line on rank 0 (contract in the task description).
+--full adds everything beyond the headline figure: the timed region repeated until the GPU phase lasts
+>= ~10 s (median reported, spread in the line), the same K steps with a per-step loss read-back,
+`roofline` (dominant kernel: the 3x3 implicit-GEMM convolution, timed live with events on the launch
+stream in a pass of its own), the forward latency per tile, and `cpu_baseline` (the CPU oracle = port
+of the reference's torch operators, timed on the host cores).
+--dump-outputs DIR writes what the last timed step computed (outputs, loss, a fixed sample of the
+updated parameters) as DIR/<name>.npy, before anything of --full runs further steps.
 """
 import argparse
 import json
@@ -195,6 +200,30 @@ def newest_record(name):
         if os.path.exists(p):
             return p
     return None
+
+
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(outdir, arrays, seed=0):
+    """``arrays`` (name -> tensor) -> ``outdir/<name>.npy`` in float32, DUMP_LIMIT_BYTES in all.  The smaller arrays are written
+    whole; one larger than its share of what is left becomes a sample of its flattened elements at positions drawn from ``seed``
+    and its size alone, so two runs with the same arguments sample the same elements."""
+    import numpy as np
+    import torch
+    os.makedirs(outdir, exist_ok=True)
+    left = DUMP_LIMIT_BYTES // 4 - 1024                      # elements (headroom for the .npy headers)
+    order = sorted(arrays, key=lambda k: arrays[k].numel())
+    for i, name in enumerate(order):
+        a = arrays[name].detach().float()
+        n = a.numel()
+        k = min(n, left // (len(order) - i))
+        if k < n:
+            idx = torch.randint(n, (k,), generator=torch.Generator().manual_seed(seed)).sort().values
+            a = a.reshape(-1)[idx.to(a.device)]
+            print(f"bench.py: {name}.npy holds {k} of {n} elements (seeded sample)", file=sys.stderr)
+        left -= k
+        np.save(os.path.join(outdir, name + ".npy"), a.cpu().numpy())
 
 
 STAGE_TAG = "[mau-bench-stage]"
@@ -543,9 +572,15 @@ def main():
     ap.add_argument("--traffic-bytes", type=float, default=None,
                     help="HBM bytes per launch of the dominant kernel from a separate rocprofv3 --pmc pass; default: the "
                          "figure committed under profiles/ for the same workload (profiles/r2/pmc_summary.json)")
-    ap.add_argument("--repeats", type=int, default=0, help="how many times the K-step timed region is run back to back (median reported); "
-                                                           "0 = as many as make the GPU phase last about 10 s")
+    ap.add_argument("--repeats", type=int, default=None, help="how many times the K-step timed region is run back to back (median reported); "
+                                                              "0 = as many as make the GPU phase last about 10 s.  Default: 1, with --full 0")
+    ap.add_argument("--full", action="store_true", help="also measure what the headline figure does not need: CPU baseline, ~10 s of "
+                                                        "repeated timed regions, loss read-back pass, per-kernel roofline, forward latency per tile")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed as DIR/<name>.npy (float32, at most 64 MB in all)")
     args = ap.parse_args()
+    if args.cpu_baseline_b32 and not args.full:
+        ap.error("--cpu-baseline-b32 is part of the CPU baseline: pass --full")
     if os.environ.get("MAU_BENCH_WORKER") != "1":
         # supervisors: before anything touches the GPU (or even imports torch)
         if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
@@ -558,7 +593,7 @@ def main():
     stage("imported")
     # the CPU baseline runs FIRST (rank 0, N = 1): the GPU phase that follows is then one contiguous stretch of the run
     cpu_rec = None
-    if int(os.environ.get("WORLD_SIZE", "1")) == 1 and args.gpus == 1 and not args.no_cpu_baseline:
+    if args.full and int(os.environ.get("WORLD_SIZE", "1")) == 1 and args.gpus == 1 and not args.no_cpu_baseline:
         cpu_rec = cpu_baseline(b32=args.cpu_baseline_b32)
 
     os.environ.setdefault("MAU_QUIET", "1")        # stdout carries the one JSON line: the constructor's announcement stays off it
@@ -602,13 +637,14 @@ def main():
     losses = torch.zeros(args.steps + args.warmup, device=dev)
 
     session = [None]            # --infer on one GPU: the app's path, an inference.GraphedInference session (one hipGraph replay per call)
+    last_out = [None]           # what the latest step returned to its caller (--dump-outputs; a graph replay's outputs live in graphed.outputs)
 
     def infer_step(i):
         if session[0] is not None:
-            session[0](x, ts, md)
+            last_out[0] = session[0](x, ts, md)
             return
         with torch.no_grad():
-            net(x, ts, md)
+            last_out[0] = net(x, ts, md)
 
     graphed = None
     # data parallel: MAU_DP_GRAPH=1 captures the step with its collectives (the supervisor's first attempt); 0 = eager, the
@@ -635,13 +671,24 @@ def main():
         opt.step()
         opt.zero_grad()
         losses[i] = loss.detach()
+        last_out[0] = out.detach()
 
     if args.infer:
         net.eval().freeze_inference()      # inference session: packed weights / folded BN coefficients computed once
         if not args.no_graph:          # (N > 1: every rank is an independent replica with a session of its own, no collective)
             session[0] = mau_amd.GraphedInference(net, x, ts, md)
+    def last_step_arrays():
+        """What the last step handed its caller: the model's outputs and, for a train step, its loss and the parameters it left
+        behind (the state the next step starts from)."""
+        arrays = {"outputs": graphed.outputs if graphed is not None else last_out[0]}
+        if not args.infer:
+            arrays["loss"] = losses[(args.warmup + args.steps - 1) % losses.numel()]
+            arrays["params"] = torch.cat([p.detach().reshape(-1).float() for p in net.parameters()])
+        return arrays
+
     timer = ConvTimer(F_)
-    timer.install()
+    if args.full:
+        timer.install()
 
     def barrier():
         if world > 1:
@@ -681,7 +728,7 @@ def main():
     # events in a graph) and not with the weight gradients on their own stream (two kernels share the chip: neither's events
     # measure it alone) -- then the same K steps are launched again afterwards, eagerly, on one stream, with the brackets
     separate_pass = session[0] is not None if args.infer else (graphed is not None or bool(F_._OVERLAP_WGRAD))
-    timer.enabled = not separate_pass
+    timer.enabled = args.full and not separate_pass
 
     def max_over_ranks(vals):
         if world == 1:
@@ -704,17 +751,19 @@ def main():
         instrumented_region = timed_region()
         timer.enabled = False
     regions = [timed_region()]
-    repeats = args.repeats
+    repeats = args.repeats if args.repeats is not None else (0 if args.full else 1)
     if repeats <= 0:      # ~10 s of contiguous GPU work, the same count on every rank (derived from the max-over-ranks first region)
         repeats = max(1, min(100, int(10.0 / max(1e-3, max_over_ranks(regions)[0]) + 0.5)))
     for _ in range(repeats - 1):
         regions.append(timed_region())
+    if args.dump_outputs and rank == 0:                      # now: what follows under --full runs further steps
+        dump_outputs(args.dump_outputs, last_step_arrays())
     regions = max_over_ranks(regions)                        # per region: the slowest rank's clock
     elapsed = statistics.median(regions)
     # the reference loop reads the loss back every step (src/train.py:258, `.detach().cpu().item()`): the same K steps with that
     # read-back (one host synchronisation per step) -- reported beside the headline figure, not instead of it
     readback_ms = None
-    if not args.infer:
+    if args.full and not args.infer:
         barrier()
         t0 = time.perf_counter()
         acc = 0.0
@@ -846,10 +895,17 @@ def main():
             "final_loss": float(losses[-1]),
             "roofline": roofline,
         }
+        if not args.full:                                   # passes of --full alone
+            del result["ms_per_step_with_loss_readback"], result["roofline"]
         result.update(fwd)
         if cpu_rec is not None:
             result["cpu_baseline"] = cpu_rec
         return json.dumps(result)
+
+    if not args.full:
+        if rank == 0:
+            print(result_line(None, {}), flush=True)
+        return finish()
 
     if world > 1 and rank == 0:
         # The measurement is in hand: print it NOW.  What follows (the event pass runs the collectives again) can only lose it;

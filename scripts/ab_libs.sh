@@ -2,7 +2,7 @@
 # Same-call A/B of two (or more) builds of libmau_hip.so with the same ABI, alternating (through gpurun: boxes differ by ~5 %, so only
 # numbers of ONE call are ever compared):
 #     bash scripts/ab_libs.sh <rounds> <label>=<path|""> [<label>=<path> ...] -- <command ...>
-#   e.g. bash scripts/ab_libs.sh 5 base=$PWD/metadata-augmented-unet-for-lst-ndvi_amd/variants/libmau_base.so final= -- python bench.py --no-cpu-baseline --repeats 12
+#   e.g. bash scripts/ab_libs.sh 5 base=$PWD/metadata-augmented-unet-for-lst-ndvi_amd/variants/libmau_base.so final= -- python bench.py --full --no-cpu-baseline --repeats 12
 # An empty path = the in-tree library.  Variant builds: scripts/build_variants.sh <file.hip> name:"-DFLAG ...".  The command's stdout is
 # printed behind a "== <label> <round>" line; a bench.py JSON line is condensed to ms_per_step / value / conv frac.
 set -u

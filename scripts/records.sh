@@ -23,7 +23,7 @@ else
 cp profiles/$RND/pmc_summary.json gpurun_out/${RND}_profiles/pmc_summary.json
 fi
 if [ -n "$A" ] && [ -z "$QUICK" ]; then
-  python bench.py --cpu-baseline-b32 --repeats 4 2>> $R/err.txt | jl > $R/bench_default_cpu_b32.json; echo "cpu b32 rc=$?"
+  python bench.py --full --cpu-baseline-b32 --repeats 4 2>> $R/err.txt | jl > $R/bench_default_cpu_b32.json; echo "cpu b32 rc=$?"
   RND=$RND python - <<'PY'
 import json, os
 rnd = os.environ["RND"]
@@ -33,23 +33,23 @@ json.dump(rec, open(f"profiles/{rnd}/cpu_baseline_b32.json", "w"), indent=1)
 print("cpu b32", rec)
 PY
 fi
-[ -n "$A" ] && { python bench.py 2>> $R/err.txt | jl > $R/bench_default.json; echo "default rc=$?"; }
+[ -n "$A" ] && { python bench.py --full 2>> $R/err.txt | jl > $R/bench_default.json; echo "default rc=$?"; }
 if [ -n "$B" ]; then
-  python bench.py --no-cpu-baseline --no-graph 2>> $R/err.txt | jl > $R/bench_default_eager.json
-  MAU_DP_GRAPH=0 python bench.py --no-cpu-baseline --force-dist 2>> $R/err.txt | jl > $R/bench_dp1_forced_eager.json
-  MAU_DP_GRAPH=1 python bench.py --no-cpu-baseline --force-dist 2>> $R/err.txt | jl > $R/bench_dp1_forced_graph.json
-  python bench.py --no-cpu-baseline --model-type unet++ --batch 16 --seq-len 828 2>> $R/err.txt | jl > $R/bench_unetpp_b16_T828.json
-  python bench.py --no-cpu-baseline --infer --size 512 --batch 8 --precision fp16 2>> $R/err.txt | jl > $R/bench_infer512_fp16.json
-  python bench.py --no-cpu-baseline --infer --size 512 --batch 1 --channels 23 --meta 8 --precision fp16 2>> $R/err.txt | jl > $R/bench_infer512_fp16_b1_c23.json
-  python bench.py --no-cpu-baseline --precision fp32 --batch 8 2>> $R/err.txt | jl > $R/bench_fp32_b8.json
+  python bench.py --full --no-cpu-baseline --no-graph 2>> $R/err.txt | jl > $R/bench_default_eager.json
+  MAU_DP_GRAPH=0 python bench.py --full --no-cpu-baseline --force-dist 2>> $R/err.txt | jl > $R/bench_dp1_forced_eager.json
+  MAU_DP_GRAPH=1 python bench.py --full --no-cpu-baseline --force-dist 2>> $R/err.txt | jl > $R/bench_dp1_forced_graph.json
+  python bench.py --full --no-cpu-baseline --model-type unet++ --batch 16 --seq-len 828 2>> $R/err.txt | jl > $R/bench_unetpp_b16_T828.json
+  python bench.py --full --no-cpu-baseline --infer --size 512 --batch 8 --precision fp16 2>> $R/err.txt | jl > $R/bench_infer512_fp16.json
+  python bench.py --full --no-cpu-baseline --infer --size 512 --batch 1 --channels 23 --meta 8 --precision fp16 2>> $R/err.txt | jl > $R/bench_infer512_fp16_b1_c23.json
+  python bench.py --full --no-cpu-baseline --precision fp32 --batch 8 2>> $R/err.txt | jl > $R/bench_fp32_b8.json
   # PMC records of the other BASELINE workloads, then their bench lines (which quote them)
   bash scripts/profile.sh ${RND}upp --no-graph --repeats 1 --model-type unet++ --batch 16
   python scripts/summarize_profile.py gpurun_out/prof_${RND}upp gpurun_out/${RND}_profiles unet++_bf16_b16_s256_c6_train > $R/profiles_summ_unetpp.txt 2>&1; echo "summ upp rc=$?"
   bash scripts/profile.sh ${RND}inf --no-graph --repeats 1 --infer --size 512 --batch 8
   python scripts/summarize_profile.py gpurun_out/prof_${RND}inf gpurun_out/${RND}_profiles unet_bf16_b8_s512_c6_infer > $R/profiles_summ_infer.txt 2>&1; echo "summ inf rc=$?"
   cp gpurun_out/${RND}_profiles/pmc_summary.json profiles/$RND/pmc_summary.json
-  python bench.py --no-cpu-baseline --model-type unet++ --batch 16 2>> $R/err.txt | jl > $R/bench_unetpp_b16.json
-  python bench.py --no-cpu-baseline --infer --size 512 --batch 8 --precision bf16 2>> $R/err.txt | jl > $R/bench_infer512_bf16_b8.json
+  python bench.py --full --no-cpu-baseline --model-type unet++ --batch 16 2>> $R/err.txt | jl > $R/bench_unetpp_b16.json
+  python bench.py --full --no-cpu-baseline --infer --size 512 --batch 8 --precision bf16 2>> $R/err.txt | jl > $R/bench_infer512_bf16_b8.json
 fi
 echo "bench lines done"
 [ -n "$A" ] && { OUT=$R/conv_layers.json timeout -k 10 300 python scripts/conv_layer_bench.py > $R/conv_layers.txt 2>&1; echo "layers rc=$?"; }

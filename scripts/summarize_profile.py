@@ -83,7 +83,7 @@ def family(pred):
     return out
 
 
-cmd = open(os.path.join(src, "command.txt")).read().strip() if os.path.exists(os.path.join(src, "command.txt")) else "python3 bench.py --steps 3 --warmup 1 --no-cpu-baseline"
+cmd = open(os.path.join(src, "command.txt")).read().strip() if os.path.exists(os.path.join(src, "command.txt")) else "python3 bench.py --full --steps 3 --warmup 1 --no-cpu-baseline"
 
 
 def calls_of(*needles):

@@ -240,7 +240,7 @@ def test_bench_self_launches_two_ranks(tmp_path):
     import json
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
     env.update(MAU_DIST_BACKEND="gloo", HSA_ENABLE_IPC_MODE_LEGACY="0")
-    common = ["--steps", "2", "--warmup", "1", "--batch", "2", "--size", "64", "--no-cpu-baseline"]
+    common = ["--full", "--steps", "2", "--warmup", "1", "--batch", "2", "--size", "64", "--no-cpu-baseline"]
     p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2"] + common, env=env, capture_output=True, text=True, timeout=600)
     assert p.returncode == 0, p.stderr[-3000:]
     lines = [ln for ln in p.stdout.splitlines() if ln.startswith("{")]
