@@ -387,6 +387,41 @@ int mau_adamw_pack_desc_fill(void* descs_host, int index, float* w, const float*
 int mau_adamw_pack_step(const void* descs, int n, int total_tiles, int dtype, const float* step, float lr, float beta1,
                         float beta2, float eps, float weight_decay, mau_stream_t stream);
 
+/* ---- the same launch for the reference's three optimizers (src/train.py:209-216), and gradient clipping (src/train.py:253-254)
+ *      inside it.  Additive to ABI 5: mau_adamw_pack_step is mau_opt_pack_step(MAU_OPT_ADAMW, grad_scale = NULL), same bits ----
+ * rule, fp32, the operation order of torch's single-tensor implementations:
+ *   MAU_OPT_ADAMW  torch.optim.AdamW (src/train.py:213-214): as above.
+ *   MAU_OPT_ADAM   torch.optim.Adam  (src/train.py:211-212), L2 decay: g <- g + wd p, then the moments and the step of AdamW
+ *                  without the decoupled decay.
+ *   MAU_OPT_SGD    torch.optim.SGD   (src/train.py:209-210), dampening 0: g <- g + wd p; buf <- momentum buf + g (a zero-filled
+ *                  buffer makes the first step buf = g, torch's first-step rule); p <- p - lr (nesterov ? g + momentum buf : buf).
+ *                  One state tensor: the rows' m is the momentum buffer (NULL when momentum == 0), v is NULL; step may be NULL.
+ * Table rows: mau_opt_pack_desc_fill = mau_adamw_pack_desc_fill that accepts m == NULL / v == NULL (same row layout,
+ * mau_adamw_pack_desc_bytes()).  grad_scale: DEVICE scalar (NULL: none) every gradient is multiplied by as it is loaded, before the
+ * weight decay -- the coefficient mau_grad_norm_clip wrote; the gradients in memory are NOT rewritten. */
+#define MAU_OPT_ADAMW 0
+#define MAU_OPT_ADAM 1
+#define MAU_OPT_SGD 2
+int mau_opt_pack_desc_fill(void* descs_host, int index, float* w, const float* grad, float* m, float* v, void* wf, void* wd,
+                           int Cout, int Cin, int tile0, int* next_tile_host);
+int mau_opt_pack_step(const void* descs, int n, int total_tiles, int dtype, int rule, const float* step, const float* grad_scale,
+                      float lr, float beta1_or_momentum, float beta2, float eps, float weight_decay, int nesterov,
+                      mau_stream_t stream);
+
+/* Global L2 norm of a set of fp32 gradients and the coefficient of torch.nn.utils.clip_grad_norm_ (src/train.py:253-254), ONE
+ * launch, no host read-back: norm_out = sqrt(sum of squares) and coef_out = min(1, max_norm / (norm + 1e-6)) (clip_coef_clamped;
+ * a non-finite gradient gives a non-finite norm, as torch does with error_if_nonfinite=False).  segs: DEVICE table of nsegs rows
+ * (mau_grad_norm_seg_bytes() each) filled on the HOST by mau_grad_norm_seg_fill: a contiguous fp32 range (ptr, n) and block0 = the
+ * first workgroup of the range = *next_block_host of the previous row (0 for row 0); total_blocks = the last row's *next_block_host.
+ * A workgroup sums the squares of mau_grad_norm_chunk() consecutive floats of one range in fp64; the workgroup that draws the last
+ * ticket adds the total_blocks partials in index order: the bits do not depend on the order the workgroups ran in.  ws: fp64
+ * workspace of total_blocks elements; tickets: a ZEROED mau_reduce_tickets_elems() buffer (left zeroed). */
+int mau_grad_norm_chunk(void);
+size_t mau_grad_norm_seg_bytes(void);
+int mau_grad_norm_seg_fill(void* segs_host, int index, const float* ptr, int64_t n, int block0, int* next_block_host);
+int mau_grad_norm_clip(const void* segs, int nsegs, int total_blocks, double* ws, unsigned* tickets, float max_norm,
+                       float* norm_out, float* coef_out, mau_stream_t stream);
+
 /* ---- loss: F.mse_loss (src/utils/losses.py:27-39) -------------------------- */
 /* loss[0] = mean((out-tgt)^2) (fp64 accumulation, fixed order); dout (optional) = 2*(out-tgt)/n;
  * partial: fp64 workspace of mau_mse_blocks(n) elements. */

@@ -20,6 +20,7 @@ LIB_PATH = os.environ.get("MAU_LIB") or os.path.join(_HERE, "libmau_hip.so")    
 MAU_F32 = 0
 MAU_BF16 = 1
 MAU_F16 = 2
+MAU_OPT_ADAMW, MAU_OPT_ADAM, MAU_OPT_SGD = 0, 1, 2
 
 _p, _i, _i64, _f, _d, _sz = C.c_void_p, C.c_int, C.c_int64, C.c_float, C.c_double, C.c_size_t
 
@@ -99,6 +100,12 @@ PROTOTYPES = {
     "mau_adamw_pack_desc_bytes": (_sz, []),
     "mau_adamw_pack_desc_fill": (_i, [_p, _i, _p, _p, _p, _p, _p, _p, _i, _i, _i, _p]),
     "mau_adamw_pack_step": (_i, [_p, _i, _i, _i, _p, _f, _f, _f, _f, _f, _p]),
+    "mau_opt_pack_desc_fill": (_i, [_p, _i, _p, _p, _p, _p, _p, _p, _i, _i, _i, _p]),
+    "mau_opt_pack_step": (_i, [_p, _i, _i, _i, _i, _p, _p, _f, _f, _f, _f, _f, _i, _p]),
+    "mau_grad_norm_chunk": (_i, []),
+    "mau_grad_norm_seg_bytes": (_sz, []),
+    "mau_grad_norm_seg_fill": (_i, [_p, _i, _p, _i64, _i, _p]),
+    "mau_grad_norm_clip": (_i, [_p, _i, _i, _p, _p, _f, _p, _p, _p]),
     "mau_sum_tensors_max": (_i, []),
     "mau_sum_tensors": (_i, [_p, _p, _i, _p, _i, _i, _i64, _i, _p]),
     "mau_emb_fold_fwd": (_i, [_p, _p, _p, _i, _i, _i, _i, _i, _p]),

@@ -99,31 +99,7 @@ static int reduce_rows_launch(const float* slab, int rows, int M, int ldrow, Out
   return check_launch("reduce_rows_kernel");
 }
 
-// ---- "the last workgroup of a column block runs the second level" ----
-// Every thread of the block has issued its partial stores.  Returns true in exactly one block per ticket: the one that
-// arrives last; by then the partials of all n blocks are visible to it.  Producer side: each storing wave drains its
-// stores (vmcnt(0)), workgroup barrier, one lane releases at agent scope and takes the ticket.  Consumer side (the last
-// arriver): agent-scope acquire (invalidates this CU's L1: a line of the partial buffer may be resident from an earlier
-// launch), its completion waited for, barrier, then plain loads.  The ticket is reset for the next launch on the stream.
-__device__ __forceinline__ bool last_block_of(unsigned* ticket, unsigned n) {
-  __shared__ unsigned s_last;
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    const unsigned t = __hip_atomic_fetch_add(ticket, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    const unsigned last = t == n - 1 ? 1u : 0u;
-    if (last) {
-      __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
-      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-      __hip_atomic_store(ticket, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    }
-    s_last = last;
-  }
-  __syncthreads();
-  return s_last != 0;
-}
+// ("the last workgroup of a column block runs the second level": last_block_of, mau_common.h)
 
 // Single-launch form of reduce_rows_launch: grid (column blocks, chunks).  Output column j reads slab column
 // j (j < split) or j - split + gap (j >= split): the BatchNorm statistics slab keeps sum and sum of squares in two

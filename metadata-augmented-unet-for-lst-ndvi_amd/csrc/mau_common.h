@@ -250,6 +250,32 @@ static inline int stream_grid(int64_t work_items, int block) {
   return (int)g;
 }
 
+// ---- "the last workgroup runs the second level" ----
+// Every thread of the block has issued its partial stores.  Returns true in exactly one block per ticket: the one that
+// arrives last; by then the partials of all n blocks are visible to it.  Producer side: each storing wave drains its
+// stores (vmcnt(0)), workgroup barrier, one lane releases at agent scope and takes the ticket.  Consumer side (the last
+// arriver): agent-scope acquire (invalidates this CU's L1: a line of the partial buffer may be resident from an earlier
+// launch), its completion waited for, barrier, then plain loads.  The ticket is reset for the next launch on the stream.
+__device__ __forceinline__ bool last_block_of(unsigned* ticket, unsigned n) {
+  __shared__ unsigned s_last;
+  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    const unsigned t = __hip_atomic_fetch_add(ticket, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    const unsigned last = t == n - 1 ? 1u : 0u;
+    if (last) {
+      __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
+      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+      __hip_atomic_store(ticket, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    }
+    s_last = last;
+  }
+  __syncthreads();
+  return s_last != 0;
+}
+
 // bn_fused.hip: the 1x1 head on an activation tensor (no BatchNorm), fast path of mau_head_fwd
 int head_fwd_fast(const void* a, int lda, const float* w, const float* b, float* out, int tanh0, int dtype, int64_t npix, int HW, int C, int Co,
                   hipStream_t stream);

@@ -25,7 +25,7 @@ from .checkpoint import build_hyperparameters, save_checkpoint
 from .config import CONFIG
 from .dist import GradSync, init_process_group_from_env
 from .model import UrbanPredictor
-from .optim import AdamW
+from .optim import SGD, Adam, AdamW, _PackOptimizer
 from .train_graph import GraphedTrainStep
 
 app = typer.Typer(add_completion=False)
@@ -105,11 +105,12 @@ def run(device: str = "", wandblog: bool = False, n_trials: int = 1, force_study
                            deep_supervision=False, temporal_embeddings=temporal_embeddings,
                            metadata_embeddings=metadata_embeddings).to(CONFIG.device)              # src/train.py:194-206
     model.set_precision(precision).train()
+    # torch.optim's rules; the convolution weights' update + re-pack is one kernel (optim.py)
     if cfg.optimizer == "SGD":                                                                # src/train.py:209-216
-        optimizer = torch.optim.SGD(model.parameters(), lr=cfg.learning_rate, momentum=cfg.momentum)
+        optimizer = SGD(model.parameters(), lr=cfg.learning_rate, momentum=cfg.momentum)
     elif cfg.optimizer == "Adam":
-        optimizer = torch.optim.Adam(model.parameters(), lr=cfg.learning_rate, weight_decay=cfg.weight_decay)
-    elif cfg.optimizer == "AdamW":      # torch.optim.AdamW's rule; the convolution weights' update + re-pack is one kernel (optim.py)
+        optimizer = Adam(model.parameters(), lr=cfg.learning_rate, weight_decay=cfg.weight_decay)
+    elif cfg.optimizer == "AdamW":
         optimizer = AdamW(model.parameters(), lr=cfg.learning_rate, weight_decay=cfg.weight_decay)
     else:
         raise NotImplementedError(f"Optimizer {cfg.optimizer} not implemented.")
@@ -141,6 +142,8 @@ def run(device: str = "", wandblog: bool = False, n_trials: int = 1, force_study
     vgen = torch.Generator().manual_seed(CONFIG.seed + 7919 + rank)
     val_loader = [synthetic_batch(cfg.batch_size, CONFIG.device, vgen) for _ in range(max(0, val_batches))]
     clip = 5.0 if cfg.gradient_clipping > 0 else 0.0                                            # src/train.py:253-254
+    if clip > 0 and isinstance(optimizer, _PackOptimizer):      # norm + coefficient in one launch, the scaling inside the fused update
+        optimizer.max_grad_norm, clip = clip, 0.0
     # one GPU: the step (forward, criterion, backward, clip, optimizer) is captured once and replayed (static shapes);
     # data parallel: eager, the RCCL collectives are launched from autograd hooks while backward still runs
     # (MAU_DP_GRAPH=1: the data-parallel step is captured too, collectives included -- train_graph.py)

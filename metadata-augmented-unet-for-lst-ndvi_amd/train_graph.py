@@ -6,7 +6,7 @@
 
 A train step of the U-Net is ~190 kernel launches of 2 us .. 400 us; launched one by one from Python the
 short ones (weight packs, slab reductions, BatchNorm finalizes, split-K sums) leave the GPU waiting for
-the host.  The C ABI allocates nothing and never synchronises, the optimizer (mau_amd.AdamW, or torch's fused
+the host.  The C ABI allocates nothing and never synchronises, the optimizer (mau_amd.AdamW / Adam / SGD, or torch's fused
 AdamW made capturable) reads its step count from device memory, and every reduction keeps its workspace in torch's caching allocator -- so the whole step is
 capturable: the first ``warmup`` calls run eagerly (they are ordinary training steps on the batches they
 are given; they also warm the allocator and set the kernels' LDS attributes), the next call captures
@@ -29,7 +29,7 @@ from typing import Callable, Optional, Sequence
 import torch
 
 from . import functional as F_
-from .optim import AdamW as _AdamW
+from .optim import _PackOptimizer
 
 
 def _make_capturable(optimizer: torch.optim.Optimizer):
@@ -69,7 +69,8 @@ def live_autograd_graph_params(params) -> list:
 
 class GraphedTrainStep:
     """``criterion(outputs, targets)`` returns the reference's loss dict (``{'total': ...}``, src/utils/losses.py) or a
-    scalar tensor.  ``clip_grad_norm``: max norm of ``torch.nn.utils.clip_grad_norm_`` (src/train.py:253-254), 0 = off.
+    scalar tensor.  ``clip_grad_norm``: max norm of ``torch.nn.utils.clip_grad_norm_`` (src/train.py:253-254), 0 = off; an optimizer
+    of ``mau_amd.optim`` takes it over as its ``max_grad_norm`` (norm and coefficient in one launch, the scaling inside the update).
     ``copy_inputs=False``: the tensors of the capturing call ARE the static buffers -- later calls must pass the same
     tensors (a resident synthetic batch, or buffers the loader fills in place); the default copies every batch in."""
 
@@ -78,6 +79,10 @@ class GraphedTrainStep:
         self.model, self.optimizer, self.criterion = model, optimizer, criterion
         self.warmup = max(1, int(warmup))
         self.clip = float(clip_grad_norm)
+        if self.clip > 0 and isinstance(optimizer, _PackOptimizer):
+            if optimizer.max_grad_norm not in (0.0, self.clip):
+                raise ValueError(f"GraphedTrainStep(clip_grad_norm={self.clip}): the optimizer already clips at {optimizer.max_grad_norm}")
+            optimizer.max_grad_norm, self.clip = self.clip, 0.0        # the optimizer clips: no clip_grad_norm_ below
         self.copy_inputs = copy_inputs
         self.grad_sync = grad_sync                 # dist.GradSync: its bucketed all-reduces (and the model's SyncBN ones) become graph nodes
         self.calls = 0
@@ -126,10 +131,10 @@ class GraphedTrainStep:
                 "stream and end in hipStreamEndCapture taking the process down.  Drop or .detach() those tensors before the "
                 "capturing call (the step itself returns detached tensors).")
         # Who re-packs the convolution weights?  torch's optimizers: the captured forward starts with the (captured) multi-tensor
-        # re-pack.  optim.AdamW writes the packs together with the update: the captured step then contains NO separate pack -- the
+        # re-pack.  The optimizers of optim.py write the packs together with the update: the captured step then contains NO separate pack -- the
         # forward of replay k reads what the optimizer of replay k - 1 (or of the last warm-up step) wrote.
         self._groups = [m._pack_group for m in self.model.modules() if hasattr(m, "_pack_group")]
-        self._self_packing = isinstance(self.optimizer, _AdamW)
+        self._self_packing = isinstance(self.optimizer, _PackOptimizer)
         if not self._self_packing:
             F_.mark_params_updated()
         torch.cuda.synchronize()

@@ -92,7 +92,7 @@ def calls_of(*needles):
 
 # what the profiled command ran, from its own launch counts: one optimizer launch per train step, one metadata-MLP forward per
 # network forward (train or eval) -- warm-up, capture, timed regions, the read-back pass, the event pass and the latency forwards
-n_steps = calls_of("adamw_pack_kernel") or calls_of("mse_kernel")
+n_steps = calls_of("opt_pack_kernel", "adamw_pack_kernel") or calls_of("mse_kernel")
 n_fwd = calls_of("meta_mlp_fwd_kernel")
 ran = f"{n_steps} train steps + {max(0, n_fwd - n_steps)} eval-mode forwards, counted from the launches of this profile"
 summary = {
