@@ -336,6 +336,18 @@ int mau_bcast_bwd(const void* dx, int lddx, int choff, float* demb, float* ws, i
 /* out (N,Co,H,W) fp32 NCHW; tanh on channel 0 iff tanh0 != 0 (the reference does so iff Co == 2). */
 int mau_head_fwd(const void* a, int lda, const float* w, const float* b, float* out, int tanh0, int dtype,
                  int N, int HW, int C, int Co, mau_stream_t stream);
+/* Head and per-sample spatial mean in ONE launch (the metadata-sensitivity sweeps keep only the mean of every output map):
+ *   means[n][o] = scale[o] * mean over HW of head(a[n])[o] + shift[o]        (fp64, shape (N, Co))
+ * Per pixel the value is the one mau_head_fwd writes, bit for bit; the (N,Co,H,W) map is never written.  scale / shift:
+ * Co fp64 values each, NULL = identity, applied once to the fp64 mean.  Sums are fp64 in a fixed order: a workgroup owns
+ * a run of pixels of ONE sample, the workgroup that draws the sample's last ticket adds the sample's partials in index
+ * order -- a sample's result does not depend on N or on the grid and is bitwise repeatable.
+ * ws: fp64 workspace of mau_head_mean_ws_elems(N, HW, Co) elements; tickets: a ZEROED mau_reduce_tickets_elems() buffer
+ * (left zeroed; see mau_reduce_rows_f64).  One launch per mau_reduce_tickets_elems() samples. */
+size_t mau_head_mean_ws_elems(int N, int HW, int Co);
+int mau_head_mean(const void* a, int lda, const float* w, const float* b, const double* scale, const double* shift,
+                  double* means, double* ws, unsigned* tickets, int tanh0, int dtype, int N, int HW, int C, int Co,
+                  mau_stream_t stream);
 /* da NHWC-ld = W^T dz with dz = dout * (1 - out^2 on the tanh channel); slab
  * [mau_head_bwd_rows][mau_head_bwd_rowlen] holds per-block partial sums: for output channel o,
  * row[o*(C8+8) + c] = partial dW[o][c] and row[o*(C8+8) + C8] = partial db[o]  (C8 = roundup(C,8)). */

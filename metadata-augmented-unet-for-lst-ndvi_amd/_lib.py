@@ -86,6 +86,8 @@ PROTOTYPES = {
     "mau_bcast_bwd_ws_elems": (_sz, [_i, _i, _i]),
     "mau_bcast_bwd": (_i, [_p, _i, _i, _p, _p, _i, _i, _i, _i, _p]),
     "mau_head_fwd": (_i, [_p, _i, _p, _p, _p, _i, _i, _i, _i, _i, _i, _p]),
+    "mau_head_mean_ws_elems": (_sz, [_i, _i, _i]),
+    "mau_head_mean": (_i, [_p, _i, _p, _p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _i, _p]),
     "mau_head_bwd": (_i, [_p, _i, _p, _p, _p, _p, _i, _p, _i, _i, _i, _i, _i, _i, _p]),
     "mau_head_bwd_rows": (_i, [_i, _i]),
     "mau_head_bwd_rowlen": (_i, [_i, _i]),

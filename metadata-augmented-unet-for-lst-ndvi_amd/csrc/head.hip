@@ -9,60 +9,126 @@ namespace mau {
 
 // 8 lanes per pixel: lane (pixel slot = tid/8, vector = tid%8) loads ONE 16-byte vector, so a wave reads
 // 8 pixels x 128 contiguous bytes per instruction; each lane keeps the weights of its 8 channels in
-// registers, three shuffle steps sum the 8 lanes, lane o writes output channel o (NCHW fp32).
+// registers, three shuffle steps sum the 8 lanes, lane o finishes output channel o.
+//
+// The per-pixel arithmetic lives in head_lane_weights + head_pixel and is shared by head_fwd_kernel (which stores the
+// value, NCHW fp32) and head_mean_kernel (which adds it to a per-sample fp64 sum): both produce the same bits per pixel.
+__device__ __forceinline__ void head_lane_weights(const float* __restrict__ w, int sub, int C, int Co, float (&wr)[HEAD_MAX_CO][8]) {
+#pragma unroll
+  for (int o = 0; o < HEAD_MAX_CO; ++o)       // weights of vector `sub` (valid when nv <= 8: the usual 64-channel head)
+#pragma unroll
+    for (int j = 0; j < 8; ++j) wr[o][j] = (o < Co && sub * 8 + j < C) ? w[o * C + sub * 8 + j] : 0.f;
+}
+
+// ap: the pixel's NHWC-ld row (read only when `live`).  Every lane of the wave must call it (the butterflies need all eight
+// lanes of a pixel).  Returns, in the lanes with live && sub < Co, head(pixel)[sub]: 1x1 conv + bias, tanh on channel 0 iff tanh0.
+template <typename T>
+__device__ __forceinline__ float head_pixel(const T* __restrict__ ap, const float* __restrict__ w, const float* __restrict__ b,
+                                            const float (&wr)[HEAD_MAX_CO][8], int sub, int nv, int C, int Co, int tanh0, bool live) {
+  float acc[HEAD_MAX_CO];
+#pragma unroll
+  for (int o = 0; o < HEAD_MAX_CO; ++o) acc[o] = 0.f;
+  if (live) {
+    if (sub < nv) {
+      const F8 x = load8<T>(ap + sub * 8);
+#pragma unroll
+      for (int o = 0; o < HEAD_MAX_CO; ++o)
+#pragma unroll
+        for (int j = 0; j < 8; ++j) acc[o] = fmaf(x.v[j], wr[o][j], acc[o]);
+    }
+    for (int v = sub + 8; v < nv; v += 8) {       // heads wider than 64 channels: weights from memory
+      const F8 x = load8<T>(ap + v * 8);
+#pragma unroll
+      for (int o = 0; o < HEAD_MAX_CO; ++o)
+        if (o < Co) {
+#pragma unroll
+          for (int j = 0; j < 8; ++j)
+            if (v * 8 + j < C) acc[o] = fmaf(x.v[j], w[o * C + v * 8 + j], acc[o]);
+        }
+    }
+  }
+#pragma unroll
+  for (int o = 0; o < HEAD_MAX_CO; ++o) {
+    acc[o] += __shfl_xor(acc[o], 1);
+    acc[o] += __shfl_xor(acc[o], 2);
+    acc[o] += __shfl_xor(acc[o], 4);
+  }
+  float r = 0.f;
+  if (live && sub < Co) {
+#pragma unroll
+    for (int o = 0; o < HEAD_MAX_CO; ++o)
+      if (o == sub) r = acc[o];
+    r += b[sub];
+    if (tanh0 && sub == 0) r = tanhf(r);
+  }
+  return r;
+}
+
 template <typename T>
 __global__ __launch_bounds__(256) void head_fwd_kernel(const T* __restrict__ a, int lda, const float* __restrict__ w,
                                                        const float* __restrict__ b, float* __restrict__ out, int tanh0, int HW,
                                                        int C, int Co, int64_t npix) {
   const int sub = threadIdx.x & 7;
   const int nv = (C + 7) >> 3;
-  float wr[HEAD_MAX_CO][8];                 // weights of vector `sub` (valid when nv <= 8: the usual 64-channel head)
-#pragma unroll
-  for (int o = 0; o < HEAD_MAX_CO; ++o)
-#pragma unroll
-    for (int j = 0; j < 8; ++j) wr[o][j] = (o < Co && sub * 8 + j < C) ? w[o * C + sub * 8 + j] : 0.f;
+  float wr[HEAD_MAX_CO][8];
+  head_lane_weights(w, sub, C, Co, wr);
   const int64_t stride = (int64_t)gridDim.x * 32;
   for (int64_t pix0 = (int64_t)blockIdx.x * 32; pix0 < npix; pix0 += stride) {      // block-uniform trip count
     const int64_t pix = pix0 + (threadIdx.x >> 3);
     const bool live = pix < npix;
-    float acc[HEAD_MAX_CO];
-#pragma unroll
-    for (int o = 0; o < HEAD_MAX_CO; ++o) acc[o] = 0.f;
-    if (live) {
-      if (sub < nv) {
-        const F8 x = load8<T>(a + pix * lda + sub * 8);
-#pragma unroll
-        for (int o = 0; o < HEAD_MAX_CO; ++o)
-#pragma unroll
-          for (int j = 0; j < 8; ++j) acc[o] = fmaf(x.v[j], wr[o][j], acc[o]);
-      }
-      for (int v = sub + 8; v < nv; v += 8) {       // heads wider than 64 channels: weights from memory
-        const F8 x = load8<T>(a + pix * lda + v * 8);
-#pragma unroll
-        for (int o = 0; o < HEAD_MAX_CO; ++o)
-          if (o < Co) {
-#pragma unroll
-            for (int j = 0; j < 8; ++j)
-              if (v * 8 + j < C) acc[o] = fmaf(x.v[j], w[o * C + v * 8 + j], acc[o]);
-          }
-      }
-    }
-#pragma unroll
-    for (int o = 0; o < HEAD_MAX_CO; ++o) {
-      acc[o] += __shfl_xor(acc[o], 1);
-      acc[o] += __shfl_xor(acc[o], 2);
-      acc[o] += __shfl_xor(acc[o], 4);
-    }
+    const float r = head_pixel<T>(a + (live ? pix : 0) * lda, w, b, wr, sub, nv, C, Co, tanh0, live);
     if (live && sub < Co) {
-      float r = 0.f;
-#pragma unroll
-      for (int o = 0; o < HEAD_MAX_CO; ++o)
-        if (o == sub) r = acc[o];
-      r += b[sub];
-      if (tanh0 && sub == 0) r = tanhf(r);
       const int64_t n = pix / HW, q = pix - n * HW;
       out[((size_t)n * Co + sub) * HW + q] = r;
     }
+  }
+}
+
+// ---- head + per-sample spatial mean in one launch: means[n][o] = scale[o] * mean_q head(a[n])[o][q] + shift[o] (fp64) ----
+// The (N,Co,H,W) map is never written.  Grid (workgroups per sample, samples): a workgroup owns HEAD_MEAN_PIX consecutive
+// pixels of ONE sample -- (32 pixel slots, stride 32) x (8 channel-vector lanes), head_fwd_kernel's mapping -- and lane `o` of a
+// slot adds head_pixel's value of channel o to an fp64 sum in pixel order.  The 32 slot sums are joined through LDS in slot
+// order into part[n][workgroup][o]; the workgroup that draws the sample's last ticket (last_block_of) adds the sample's
+// partials in workgroup order and applies 1/HW, scale and shift once.  The number of workgroups per sample depends on HW
+// alone: a sample's result does not depend on N, on the grid or on the order the workgroups ran in.
+constexpr int HEAD_MEAN_PIX = 1024;
+
+template <typename T>
+__global__ __launch_bounds__(256) void head_mean_kernel(const T* __restrict__ a, int lda, const float* __restrict__ w,
+                                                        const float* __restrict__ b, const double* __restrict__ scale,
+                                                        const double* __restrict__ shift, double* part, unsigned* tickets,
+                                                        double* __restrict__ means, int tanh0, int HW, int C, int Co, int n0) {
+  __shared__ double red[HEAD_MAX_CO][32];
+  const int sub = threadIdx.x & 7, ps = threadIdx.x >> 3;
+  const int nv = (C + 7) >> 3;
+  const int n = n0 + blockIdx.y, bps = gridDim.x;
+  float wr[HEAD_MAX_CO][8];
+  head_lane_weights(w, sub, C, Co, wr);
+  const int q0 = blockIdx.x * HEAD_MEAN_PIX;
+  const int q1 = q0 + HEAD_MEAN_PIX < HW ? q0 + HEAD_MEAN_PIX : HW;
+  const T* an = a + (size_t)n * HW * lda;
+  double s = 0.0;
+  for (int q = q0; q < q1; q += 32) {                      // block-uniform trip count
+    const int p = q + ps;
+    const bool live = p < q1;
+    const float r = head_pixel<T>(an + (size_t)(live ? p : q0) * lda, w, b, wr, sub, nv, C, Co, tanh0, live);
+    if (live && sub < Co) s += (double)r;
+  }
+  if (sub < HEAD_MAX_CO) red[sub][ps] = s;
+  __syncthreads();
+  if (threadIdx.x < Co) {
+    double t = 0.0;
+    for (int k = 0; k < 32; ++k) t += red[threadIdx.x][k];
+    part[((size_t)n * bps + blockIdx.x) * Co + threadIdx.x] = t;
+  }
+  if (!last_block_of(tickets + blockIdx.y, (unsigned)bps)) return;
+  if (threadIdx.x < Co) {                                  // level 2: the sample's partials in workgroup order
+    double t = 0.0;
+    for (int k = 0; k < bps; ++k) t += part[((size_t)n * bps + k) * Co + threadIdx.x];
+    double m = t / (double)HW;
+    if (scale != nullptr) m *= scale[threadIdx.x];
+    if (shift != nullptr) m += shift[threadIdx.x];
+    means[(size_t)n * Co + threadIdx.x] = m;
   }
 }
 
@@ -389,6 +455,29 @@ int mau_head_fwd(const void* a, int lda, const float* w, const float* b, float* 
   const int grid = stream_grid(npix * 8, 256);
   MAU_DISPATCH_DTYPE(dtype, MAU_LAUNCH(head_fwd_kernel<T>, dim3(grid), dim3(256), 0, (hipStream_t)stream, (const T*)a, lda, w, b, out, tanh0, HW, C, Co, npix));
   return check_launch("head_fwd_kernel");
+}
+
+size_t mau_head_mean_ws_elems(int N, int HW, int Co) {
+  if (N <= 0 || HW <= 0 || Co <= 0) return 0;
+  return (size_t)N * ceil_div(HW, HEAD_MEAN_PIX) * Co;
+}
+
+int mau_head_mean(const void* a, int lda, const float* w, const float* b, const double* scale, const double* shift, double* means,
+                  double* ws, unsigned* tickets, int tanh0, int dtype, int N, int HW, int C, int Co, mau_stream_t stream) {
+  MAU_REQUIRE(a && w && b && means && ws && tickets && N > 0 && HW > 0 && C > 0, "head_mean: bad arguments");
+  MAU_REQUIRE(Co >= 1 && Co <= HEAD_MAX_CO, "head_mean: out_channels must be in [1,%d]", HEAD_MAX_CO);
+  MAU_REQUIRE(lda % 8 == 0 && lda >= round_up(C, 8), "head_mean: bad ld");
+  MAU_REQUIRE(HW <= (1 << 30), "head_mean: images of at most 2^30 pixels");
+  const int bps = ceil_div(HW, HEAD_MEAN_PIX);
+  // one ticket per sample: mau_reduce_tickets_elems() samples per launch (the sweeps run 50 at a time: one launch)
+  const int per = mau_reduce_tickets_elems();
+  for (int n0 = 0; n0 < N; n0 += per) {
+    const int nn = N - n0 < per ? N - n0 : per;
+    MAU_DISPATCH_DTYPE(dtype, MAU_LAUNCH(head_mean_kernel<T>, dim3(bps, nn), dim3(256), 0, (hipStream_t)stream, (const T*)a, lda, w, b, scale, shift, ws, tickets, means, tanh0, HW, C, Co, n0));
+    const int st = check_launch("head_mean_kernel");
+    if (st != 0) return st;
+  }
+  return 0;
 }
 
 int mau_head_bwd_rows(int N, int HW) { return ceil_div((int64_t)N * HW, HEAD_PIX_PER_BLOCK); }

@@ -301,6 +301,16 @@ class _NetBase(nn.Module):
         return F_.Head.apply(a.t, a.C, self.final.weight, self.final.bias)
 
 
+def _sweep_check(net, maps=None):
+    """Preconditions of the metadata sweeps (one tile x B metadata vectors, encoder column computed once)."""
+    if net.training:
+        raise RuntimeError("a metadata sweep is an eval-mode path (BatchNorm must use running statistics)")
+    if getattr(net, "deep_supervision", False):
+        raise ValueError("a metadata sweep needs a single output: deep_supervision=True is not supported")
+    if maps is not None and maps.shape[0] != 1:
+        raise ValueError("a metadata sweep expects a single tile: maps.shape[0] == 1")
+
+
 class UrbanPredictor_unet(_NetBase):
     """src/model.py:195-292."""
 
@@ -404,32 +414,39 @@ class UrbanPredictor_unet(_NetBase):
         maps (1,C,H,W); temp_series (1,T) or (B,T); metadata (B,F).  Returns (B,out_channels,H,W), identical to
         ``self(maps.expand(B,...), temp_series.expand(B,...), metadata)`` in eval mode.
         """
-        if self.training:
-            raise RuntimeError("forward_metadata_sweep is an eval-mode path (BatchNorm must use running statistics)")
-        if maps.shape[0] != 1:
-            raise ValueError("forward_metadata_sweep expects a single tile: maps.shape[0] == 1")
-        B = metadata.shape[0]
-        if temp_series.shape[0] == 1 and B > 1:
-            temp_series = temp_series.expand(B, -1)
-        temporal_emb = self.temporal_encoder(temp_series) if self.temporal_embeddings else None
-        meta_emb = self.meta_encoder(metadata) if self.metadata_embeddings else None
+        return self._head(self._sweep_trunk(self._sweep_encoder(maps), temp_series, metadata))
+
+    @torch.no_grad()
+    def _sweep_encoder(self, maps):
+        """The metadata-independent part of a sweep at batch 1: (x0_0, x1_0, x2_0, x3_0, pool(x3_0))."""
+        _sweep_check(self, maps)
         x = self._entry(maps)
         x0_0 = self.conv0_0(x)
         x1_0 = self.conv1_0(self._pool(x0_0))
         x2_0 = self.conv2_0(self._pool(x1_0))
         x3_0 = self.conv3_0(self._pool(x2_0))
-        x4_0 = self._pool(x3_0)
+        return x0_0, x1_0, x2_0, x3_0, self._pool(x3_0)
+
+    @torch.no_grad()
+    def _sweep_trunk(self, enc, temp_series, metadata) -> Act:
+        """Sweep trunk: bottleneck and decoder at batch B = metadata.shape[0] on the broadcast encoder activations, up to the last
+        block's activation (the input of the 1x1 head)."""
+        _sweep_check(self)
+        B = metadata.shape[0]
+        if temp_series.shape[0] == 1 and B > 1:
+            temp_series = temp_series.expand(B, -1)
+        temporal_emb = self.temporal_encoder(temp_series) if self.temporal_embeddings else None
+        meta_emb = self.meta_encoder(metadata) if self.metadata_embeddings else None
 
         def rep(a: Act) -> Act:          # batch broadcast of an encoder activation (data movement only)
             return Act(a.t.expand(B, -1, -1, -1).contiguous(), a.C)
 
-        x0_0, x1_0, x2_0, x3_0, x4_0 = rep(x0_0), rep(x1_0), rep(x2_0), rep(x3_0), rep(x4_0)
+        x0_0, x1_0, x2_0, x3_0, x4_0 = (rep(a) for a in enc)
         x4_0 = self._fused_block(self.conv4_0, x4_0, [e for e in (temporal_emb, meta_emb) if e is not None])
         x3_1 = self._dec(self.conv3_1, x3_0, x4_0)
         x2_1 = self._dec(self.conv2_1, x2_0, x3_1)
         x1_1 = self._dec(self.conv1_1, x1_0, x2_1)
-        x0_1 = self._dec(self.conv0_1, x0_0, x1_1)
-        return self._head(x0_1)
+        return self._dec(self.conv0_1, x0_0, x1_1)
 
 
 class UrbanPredictor_unetpp(_NetBase):
@@ -557,6 +574,56 @@ class UrbanPredictor_unetpp(_NetBase):
                     for a, f in ((x0_1.take(), self.final1), (x0_2.take(), self.final2), (x0_3.take(), self.final3), (x0_4, self.final4))]
         # x^{0,4} is read only by the 1x1 head: the block returns final(x^{0,4}) (src/model.py:187-193)
         return self._node(self.conv0_4, last, x1_3, emb, rows=use_rows, head=self.final)
+
+    # -- metadata sweep (test/metadata_sensitivity.py:294-311, :408-419: one tile repeated B times, only the metadata varies) --
+    # The encoder column x^{0..4,0} never sees the embeddings (src/model.py:123-135): it runs once at batch 1; the ten decoder
+    # nodes run at batch B.  (Not named forward_metadata_sweep: ``UrbanPredictor.forward_metadata_sweep`` stays U-Net only;
+    # the public entry for both networks is ``mau_amd.sensitivity``.)
+    @torch.no_grad()
+    def _sweep_encoder(self, maps):
+        """The metadata-independent part of a sweep at batch 1: (x0_0, x1_0, x2_0, x3_0, x4_0)."""
+        _sweep_check(self, maps)
+        x = self._entry(maps)
+        x0_0 = self.conv0_0(x)
+        x1_0 = self.conv1_0(self._pool(x0_0))
+        x2_0 = self.conv2_0(self._pool(x1_0))
+        x3_0 = self.conv3_0(self._pool(x2_0))
+        return x0_0, x1_0, x2_0, x3_0, self.conv4_0(self._pool(x3_0))
+
+    @torch.no_grad()
+    def _sweep_trunk(self, enc, temp_series, metadata) -> Act:
+        """Sweep trunk: every node x^{i,j>=1} at batch B = metadata.shape[0] on the broadcast encoder column, through the routes
+        of ``forward`` (row buffers, virtual concat), up to x^{0,4} (the input of the 1x1 head)."""
+        _sweep_check(self)
+        B = metadata.shape[0]
+        if temp_series.shape[0] == 1 and B > 1:
+            temp_series = temp_series.expand(B, -1)
+        emb = torch.cat([self.temporal_encoder(temp_series), self.meta_encoder(metadata)], dim=1).float()
+        nb0 = self.conv0_0.conv2.out_channels
+        use_rows = self._rt.dtype != torch.float32 and nb0 % 64 == 0 and _VIRTUAL_CONCAT
+
+        def row(a: Act, slots: int):
+            """Batch broadcast of an encoder activation (data movement only) -- into slot 0 of its row's buffer when the forward
+            keeps one; returns (the broadcast activation, the row's remaining slots)."""
+            if not use_rows or slots == 1:
+                return Act(a.t.expand(B, -1, -1, -1).contiguous(), a.C), [None] * (slots - 1)
+            buf = torch.empty((B, a.H, a.W, slots * a.C), dtype=a.t.dtype, device=a.t.device)
+            views = [buf[..., j * a.C:(j + 1) * a.C] for j in range(slots)]
+            views[0].copy_(a.t.expand(B, -1, -1, -1))
+            return Act(views[0], a.C), views[1:]
+
+        (x0_0, r0), (x1_0, r1), (x2_0, r2) = row(enc[0], 4), row(enc[1], 3), row(enc[2], 2)
+        x3_0, x4_0 = row(enc[3], 1)[0], row(enc[4], 1)[0]
+        x0_1 = self._node(self.conv0_1, [x0_0], x1_0, emb, r0[0])
+        x1_1 = self._node(self.conv1_1, [x1_0], x2_0, emb, r1[0])
+        x0_2 = self._node(self.conv0_2, [x0_0, x0_1], x1_1, emb, r0[1])
+        x2_1 = self._node(self.conv2_1, [x2_0], x3_0, emb, r2[0])
+        x1_2 = self._node(self.conv1_2, [x1_0, x1_1], x2_1, emb, r1[1])
+        x0_3 = self._node(self.conv0_3, [x0_0, x0_1, x0_2], x1_2, emb, r0[2])
+        x3_1 = self._node(self.conv3_1, [x3_0], x4_0, emb, rows=use_rows)
+        x2_2 = self._node(self.conv2_2, [x2_0, x2_1], x3_1, emb, rows=use_rows)
+        x1_3 = self._node(self.conv1_3, [x1_0, x1_1, x1_2], x2_2, emb, rows=use_rows)
+        return self._node(self.conv0_4, [x0_0, x0_1, x0_2, x0_3], x1_3, emb, rows=use_rows)
 
 
 class UrbanPredictor(nn.Module):
