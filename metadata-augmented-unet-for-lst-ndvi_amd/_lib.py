@@ -40,7 +40,7 @@ PROTOTYPES = {
     "mau_conv3x3_pack_desc_fill": (_i, [_p, _i, _p, _p, _p, _i, _i, _i, _i, _p]),
     "mau_conv3x3_pack_weights_multi": (_i, [_p, _i, _i, _i, _p]),
     "mau_conv3x3_num_pixel_tiles": (_i, [_i, _i, _i, _i, _i]),
-    "mau_conv3x3_variant": (_i, [_i, _i, _i, _i, _i, _p, _p, _p]),
+    "mau_conv3x3_variant": (_i, [_i, _i, _i, _i, _i, _i, _p, _p, _p, _p]),
     "mau_conv3x3_first_max_channels": (_i, []),
     "mau_conv3x3_first_rows": (_i, [_i, _i, _i]),
     "mau_conv3x3_first_wgrad_ws_elems": (_sz, [_i, _i, _i, _i]),

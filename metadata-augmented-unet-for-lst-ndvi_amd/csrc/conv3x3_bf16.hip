@@ -1125,6 +1125,13 @@ static int launch(const ConvP& p, hipStream_t st) {
     return MAU_ERR_ARG;
   }
   const int nPixTiles = p.N * tilesX * tilesY;
+  // the caller sized the statistics slab by the query, the kernel writes WM rows per pixel tile: a variant rule that lets the two
+  // drift apart must not reach the device
+  if (p.slab != nullptr && G::WM * nPixTiles != conv_bf16_v2_num_pixel_tiles(p.N, p.H, p.W, p.Cout)) {
+    set_error("conv3x3_fwd: the <%d,%d,%d> tiling writes %d statistics slab rows, mau_conv3x3_num_pixel_tiles reports %d", BN, MT, NW,
+              G::WM * nPixTiles, conv_bf16_v2_num_pixel_tiles(p.N, p.H, p.W, p.Cout));
+    return MAU_ERR_ARG;
+  }
   const int nCt = p.CoutPad / BN;
   // fewer pixel tiles than XCDs (single-tile inference at the deep levels): "every XCD owns a range of pixel tiles" would leave XCDs
   // without work -- the items go out in plain order instead (item I = (pixel tile I / nCt, cout tile I % nCt) on XCD I % 8)
@@ -1219,10 +1226,13 @@ static inline Variant pick_variant(int CoutPad, int N, int H, int W, int Cin) {
   // slab is fetched by both (L2 hits; 74 instead of 55 DMA bytes per pixel) -- which is why the choice depends on K (round 6,
   // profiles/r6/level0_tile_form_by_k.txt, same call, alternating): K = 64: <64,4,4> 3-5 % faster; K = 192: equal; K = 208..400 (the
   // U-Net++'s full-resolution nodes): the one 8-wave workgroup on the 64 x 16 tile <64,4,8> 3-5 % faster forward -- the epilogue is a
-  // seventh to a thirteenth of such an item and the DMA bytes are what is left.  Both forms write the same statistics slab geometry
-  // (conv_bf16_v2_num_pixel_tiles does not know Cin).  Cin = 0: unknown (the slab-geometry query).
-  static const int l0 = getenv("MAU_CONV_L0") ? atoi(getenv("MAU_CONV_L0")) : -1;      // test hook: 0 / 1 force <64,4,8> / <64,4,4> (both forms stay under the exact big-tile tests)
-  if (!wide && best.th == 64 && (l0 < 0 ? Cin <= 192 : l0 != 0)) best = {32, 4, 64};
+  // seventh to a thirteenth of such an item and the DMA bytes are what is left.
+  // The statistics slab is sized by conv_bf16_v2_num_pixel_tiles, which does not know Cin (Cin = 0: unknown, the slab-geometry
+  // query) and so counts the rows of <64,4,4>: 4 * ceil(H/32) per tile column and image.  <64,4,8> writes 8 * ceil(H/64), which is the
+  // same number only while ceil(H/32) is even -- the K rule applies to those heights alone (H = 256, 250: the measured ones); at any
+  // other height <64,4,4> runs whatever Cin is.  v2::launch refuses a slab whose row count differs from the query's.
+  static const int l0 = getenv("MAU_CONV_L0") ? atoi(getenv("MAU_CONV_L0")) : -1;      // test hook: 0 / 1 force <64,4,8> / <64,4,4> in the query and the launch alike (both forms stay under the exact big-tile tests)
+  if (!wide && best.th == 64 && (l0 < 0 ? Cin <= 192 || ceil_div(H, 32) % 2 != 0 : l0 != 0)) best = {32, 4, 64};
   return best;
 }
 }  // namespace v2

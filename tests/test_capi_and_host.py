@@ -60,11 +60,74 @@ def test_library_exports_every_header_symbol():
     assert _lib.conv3x3_variant(_lib.MAU_BF16, 1, 32, 32, 1024, Cin=1024) == (8, 4, 64, 2)      # B = 1 conv4_0.conv2: 128 items on 256 CUs
     assert _lib.conv3x3_variant(_lib.MAU_BF16, 8, 32, 32, 1024, Cin=1024)[3] == 1              # B = 8: the chip is full, one K group
     assert _lib.conv3x3_variant(_lib.MAU_BF16, 1, 32, 32, 1024, Cin=48)[3] == 1                # three stages: odd, no K groups
+    # the 13 layer shapes of the B = 32, 256 x 256 U-Net step (the bench's headline) keep the variants they were measured with
+    from tests.test_dispatch_geometry_host import UNET_B32_VARIANTS
+    for Cin, Cout, H, want in UNET_B32_VARIANTS:
+        assert _lib.conv3x3_variant(_lib.MAU_BF16, 32, H, H, Cout, Cin=Cin) == want, (Cin, Cout, H)
     # the fp32 parity mode also writes split-K partial slabs (plain stores + fixed-order sum: no float atomics anywhere)
     s32 = _lib.lib.mau_conv3x3_wgrad_splits(_lib.MAU_F32, 32, 32, 32, 512, 1536)
     assert 1 <= s32 <= 32 * 4 * 2 and s32 * 9 * 512 * 1536 * 4 <= 256 << 20
     assert _lib.lib.mau_conv3x3_wgrad_acc_elems(_lib.MAU_F32, 32, 32, 32, 512, 1536) == s32 * 9 * 512 * 1536
     assert _lib.lib.mau_reduce_tickets_elems() >= 2 * 1024 // 64
+
+
+def header_prototypes():
+    """{name: (return kind, [argument kinds])} of every function declared in include/mau_hip.h; a kind is the ctypes type the binding
+    must use: any pointer and mau_stream_t -> c_void_p (the ``const char*`` RETURN -> c_char_p), scalars -> the matching ctypes type."""
+    import ctypes as C
+    scalars = {"int": C.c_int, "int64_t": C.c_int64, "float": C.c_float, "double": C.c_double, "size_t": C.c_size_t}
+    txt = open(os.path.join(ROOT, "include", "mau_hip.h")).read()
+    txt = re.sub(r"/\*.*?\*/", "", txt, flags=re.S)
+    txt = re.sub(r"//[^\n]*", "", txt)
+    txt = re.sub(r"^\s*#[^\n]*$", "", txt, flags=re.M)                 # (comments are gone: no #define continues on another line)
+
+    def kind(decl, what, is_return=False):
+        words = decl.replace("*", " * ").split()
+        if "*" in words:
+            if is_return:
+                assert words == ["const", "char", "*"], (what, decl)
+                return C.c_char_p
+            return C.c_void_p
+        words = [w for w in words if w != "const"]
+        if not is_return:
+            assert len(words) == 2, f"{what}: cannot read the parameter {decl!r}"       # type + name
+            words = words[:1]
+        assert len(words) == 1, (what, decl)
+        if words[0] == "mau_stream_t":
+            return C.c_void_p
+        assert words[0] in scalars, f"{what}: no ctypes kind for {decl!r}"
+        return scalars[words[0]]
+
+    protos = {}
+    for m in re.finditer(r"([A-Za-z_][\w\s\*]*?)\b(mau_[a-z0-9_]+)\s*\(([^()]*)\)\s*;", txt):
+        ret, name, args = m.group(1), m.group(2), m.group(3).strip()
+        assert name not in protos, name
+        params = [] if args == "void" else [a.strip() for a in args.split(",")]
+        protos[name] = (kind(ret, name, True), [kind(a, name) for a in params])
+    return protos
+
+
+def test_binding_table_matches_header_prototypes():
+    """``_lib.PROTOTYPES`` against the header, by KIND: return type, argument count, and pointer / int / int64 / float / double / size_t
+    per argument, for every entry point.  (ctypes passes surplus arguments of a cdecl call without complaint and an int in a pointer
+    slot lands in the same register: a table row with too few or mistyped entries "works" until a 64-bit value or a float meets it.)"""
+    import mau_amd  # noqa: F401
+    from mau_amd import _lib
+    protos = header_prototypes()
+    syms = header_symbols()
+    assert sorted(protos) == syms, set(protos) ^ set(syms)              # a prototype the parser cannot read fails here, it is not skipped
+    assert len(protos) == len(_lib.PROTOTYPES) >= 93
+    wrong = {}
+    for name, (ret, args) in protos.items():
+        bret, bargs = _lib.PROTOTYPES[name]
+        if bret is not ret or len(bargs) != len(args) or any(a is not b for a, b in zip(bargs, args)):
+            wrong[name] = f"header {ret.__name__}({', '.join(a.__name__ for a in args)}) != binding {bret.__name__}({', '.join(a.__name__ for a in bargs)})"
+    assert not wrong, wrong
+    # ... and the loaded functions carry exactly the table's types
+    for name, (ret, args) in protos.items():
+        fn = getattr(_lib.lib, name)
+        assert fn.restype is ret and list(fn.argtypes) == args, name
+    assert len(protos["mau_conv3x3_variant"][1]) == 10
 
 
 def test_missing_library_fails_loudly(tmp_path, monkeypatch):
