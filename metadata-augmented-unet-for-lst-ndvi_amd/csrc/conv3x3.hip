@@ -456,9 +456,13 @@ static size_t wgrad_lds_bytes() {
 }
 
 template <typename T>
-static int launch_conv(const ConvP& p, hipStream_t st) {
+static int launch_conv(const ConvP& q, hipStream_t st) {
   const size_t lds = conv_lds_bytes<T>();
   MAU_LDS_ATTR(lds, &conv3x3_igemm_kernel<T>);
+  ConvP p = q;
+  p.tilesX = ceil_div(p.W, TW);
+  p.tilesY = ceil_div(p.H, TH);
+  p.nChunks = ceil_div(p.C0 + p.C1 + p.E, PackKC<T>::value);
   dim3 grid(p.N * p.tilesX * p.tilesY, p.CoutPad / BN);
   MAU_LAUNCH(conv3x3_igemm_kernel<T>, grid, dim3(NT), lds, st, p);
   return check_launch("conv3x3_igemm_kernel");
@@ -495,6 +499,18 @@ __global__ void cast_f32_to_lp_kernel(const float* __restrict__ src, T* __restri
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i < n) dst[i] = (T)src[i];
 }
+// The kernel arguments of a forward launch, from the entry point's.  The tile fields (tilesX, tilesY, nChunks) and the 16-bit
+// launcher's xcdShift / fast belong to whoever launches: launch_conv<float> above, the launch plan of conv3x3_bf16.hip.
+static ConvP conv_params(const void* x, int ldx, int C0, const void* x1, int ldx1, int C1, const float* emb, int E, const void* wpk,
+                         const float* bias, const float* post_scale, const float* post_shift, void* y, int ldy, int Cout, float* slab,
+                         int N, int H, int W) {
+  ConvP p{};
+  p.x = x; p.ldx = ldx; p.C0 = C0; p.x1 = C1 > 0 ? x1 : nullptr; p.ldx1 = C1 > 0 ? ldx1 : 0; p.C1 = C1;
+  p.emb = emb; p.emb_lp = nullptr; p.E = E; p.w = wpk; p.bias = bias; p.post_scale = post_scale; p.post_shift = post_shift; p.y = y; p.ldy = ldy;
+  p.Cout = Cout; p.CoutPad = round_up(Cout, 64); p.slab = slab; p.N = N; p.H = H; p.W = W;
+  return p;
+}
+
 static void cast_emb(const float* emb, void* ws, int n, bool f16v, hipStream_t st) {
   if (f16v) MAU_LAUNCH(cast_f32_to_lp_kernel<f16>, dim3(ceil_div(n, 256)), dim3(256), 0, st, emb, (f16*)ws, n);
   else MAU_LAUNCH(cast_f32_to_lp_kernel<bf16>, dim3(ceil_div(n, 256)), dim3(256), 0, st, emb, (bf16*)ws, n);
@@ -572,12 +588,7 @@ int mau_conv3x3_fwd2(const void* x, int ldx, int C0, const void* x1, int ldx1, i
   MAU_REQUIRE(E >= 0 && (E == 0 || (emb && E % 8 == 0 && (C0 + C1) % 8 == 0)), "conv3x3_fwd: broadcast source needs E%%8==0 and (C0+C1)%%8==0");
   MAU_REQUIRE(((uintptr_t)x % 16) == 0 && ((uintptr_t)y % 16) == 0 && ((uintptr_t)wpk % 16) == 0, "conv3x3_fwd: pointers must be 16-byte aligned");
   MAU_REQUIRE((post_scale == nullptr) == (post_shift == nullptr), "conv3x3_fwd: post_scale and post_shift come together");
-  ConvP p;
-  p.x = x; p.ldx = ldx; p.C0 = C0; p.x1 = C1 > 0 ? x1 : nullptr; p.ldx1 = C1 > 0 ? ldx1 : 0; p.C1 = C1;
-  p.emb = emb; p.emb_lp = nullptr; p.E = E; p.w = wpk; p.bias = bias; p.post_scale = post_scale; p.post_shift = post_shift; p.y = y; p.ldy = ldy;
-  p.Cout = Cout; p.CoutPad = round_up(Cout, 64); p.slab = slab; p.N = N; p.H = H; p.W = W;
-  p.tilesX = ceil_div(W, TW); p.tilesY = ceil_div(H, TH);
-  p.nChunks = ceil_div(C0 + C1 + E, mau_conv3x3_kc(dtype));
+  ConvP p = conv_params(x, ldx, C0, x1, ldx1, C1, emb, E, wpk, bias, post_scale, post_shift, y, ldy, Cout, slab, N, H, W);
   hipStream_t st = (hipStream_t)stream;
   if (dtype == MAU_F32) return launch_conv<float>(p, st);
   if (dtype == MAU_BF16 || dtype == MAU_F16) {
@@ -605,12 +616,7 @@ int mau_conv3x3_fwd_pool(const void* x, int ldx, int C0, const void* wpk, const 
     return rc != MAU_OK ? rc : mau_maxpool2x2_fwd(y, ldy, pooled, ldpool, dtype, N, H, W, Cout, stream);
   }
   MAU_REQUIRE(dtype == MAU_BF16 || dtype == MAU_F16, "bad dtype %d", dtype);
-  ConvP p;
-  p.x = x; p.ldx = ldx; p.C0 = C0; p.x1 = nullptr; p.ldx1 = 0; p.C1 = 0;
-  p.emb = nullptr; p.emb_lp = nullptr; p.E = 0; p.w = wpk; p.bias = bias; p.post_scale = post_scale; p.post_shift = post_shift; p.y = y; p.ldy = ldy;
-  p.Cout = Cout; p.CoutPad = round_up(Cout, 64); p.slab = nullptr; p.N = N; p.H = H; p.W = W;
-  p.tilesX = ceil_div(W, TW); p.tilesY = ceil_div(H, TH);
-  p.nChunks = ceil_div(C0, mau_conv3x3_kc(dtype));
+  ConvP p = conv_params(x, ldx, C0, nullptr, 0, 0, nullptr, 0, wpk, bias, post_scale, post_shift, y, ldy, Cout, nullptr, N, H, W);
   p.pool = pooled; p.ldpool = ldpool;
   return launch_conv_bf16_v2(p, dtype == MAU_F16, (hipStream_t)stream);
 }

@@ -227,6 +227,21 @@ struct Geo {
   static_assert(LDS <= 160 * 1024, "LDS budget");
 };
 
+// The seven tilings the library instantiates, each row read off Geo<> itself.  The variant rule (pick_variant) returns an index into
+// this table, the launch plan (ConvPlan) carries it, the per-translation-unit dispatcher switches over it.
+struct Tiling {
+  int bn, mt, nw;                  // Geo<BN, MT, NW>
+  int th, wm;                      // tile rows; wave rows = statistics-slab rows per pixel tile
+  size_t lds;
+};
+template <int BN, int MT, int NW>
+constexpr Tiling tiling_of() {
+  return {BN, MT, NW, Geo<BN, MT, NW>::TH, Geo<BN, MT, NW>::WM, Geo<BN, MT, NW>::LDS};
+}
+enum TilingId { T128_4_8, T128_2_8, T64_1_4, T64_2_4, T64_4_4, T64_2_8, T64_4_8, N_TILINGS };
+constexpr Tiling kTilings[N_TILINGS] = {tiling_of<128, 4, 8>(), tiling_of<128, 2, 8>(), tiling_of<64, 1, 4>(), tiling_of<64, 2, 4>(),
+                                        tiling_of<64, 4, 4>(), tiling_of<64, 2, 8>(),  tiling_of<64, 4, 8>()};
+
 // wave-uniform operands of the loader (see the kernel's "per-lane DMA slots" comment)
 struct LoaderArgs {
   unsigned long long xa, x1a, wa, w_stage_bytes, zero_a;
@@ -1095,102 +1110,13 @@ template __global__ void conv3x3_bf16_kernel<MAU_CONV_DEV_ONE>(ConvP, int, int, 
 }  // namespace v2
 }  // namespace mau
 #else
-template <int BN, int MT, int NW, int EPI, bool F16>
-static int launch(const ConvP& p, hipStream_t st) {
-  using G = Geo<BN, MT, NW>;
-  MAU_LDS_ATTR(G::LDS, &conv3x3_bf16_kernel<BN, MT, NW, EPI, F16, true, false>);
-  MAU_LDS_ATTR(G::LDS, &conv3x3_bf16_kernel<BN, MT, NW, EPI, F16, false, false>);
-  if constexpr (MT == 4) {
-    MAU_LDS_ATTR(G::LDS, &conv3x3_bf16_kernel<BN, MT, NW, EPI, F16, true, true>);
-    MAU_LDS_ATTR(G::LDS, (&conv3x3_bf16_kernel<BN, MT, NW, EPI, F16, true, true, true>));
-  }
-  constexpr bool HAS_KG = has_k_groups(BN, MT, NW) && EPI != EPI_STATS;       // the under-filled-layer forms <64,1,4> / <64,2,4>
-  if constexpr (HAS_KG) MAU_LDS_ATTR(2 * G::LDS, (&conv3x3_bf16_kernel<BN, MT, NW, EPI, F16, true, false, false, 2>));
-  const DeviceShape ds = device_shape();
-  const int tilesX = ceil_div(p.W, TW), tilesY = ceil_div(p.H, G::TH);
-  ConvP q = p;
-  q.tilesX = tilesX;
-  q.tilesY = tilesY;
-  q.nChunks = ceil_div(p.C0 + p.C1 + p.E, KC);
-  // buffer-addressed halo loads: every 16-channel stage inside one tensor's (zero-padded) pixel row, 31-bit byte offsets
-  const long long px = (long long)p.N * p.H * p.W;
-  // (with a broadcast embedding behind the tensors: the tensors end on a stage boundary and the embedding fills whole stages;
-  //  the lane offset of an embedding stage is derived from the source-0 offset: its 16-byte-half bit needs 2 * ldx % 32 == 0)
-  const bool emb_ok = p.E == 0 || (p.emb_lp != nullptr && p.E % KC == 0 && (p.C0 + p.C1) % KC == 0 && p.ldx % KC == 0);
-  const bool one = p.C1 == 0 && p.ldx % KC == 0 && round_up(p.C0, KC) <= p.ldx;
-  const bool two = p.C1 > 0 && p.C0 % KC == 0 && p.C0 <= p.ldx && round_up(p.C1, KC) <= p.ldx1;
-  q.fast = emb_ok && (one || two) && px * p.ldx * 2 < (1ll << 31) && px * p.ldx1 * 2 < (1ll << 31) ? 1 : 0;
-  if ((long long)q.nChunks * 9 * p.CoutPad * KC * 2 >= (1ll << 31)) {
-    set_error("conv3x3_fwd: packed weights beyond 2 GiB");
-    return MAU_ERR_ARG;
-  }
-  const int nPixTiles = p.N * tilesX * tilesY;
-  // the caller sized the statistics slab by the query, the kernel writes WM rows per pixel tile: a variant rule that lets the two
-  // drift apart must not reach the device
-  if (p.slab != nullptr && G::WM * nPixTiles != conv_bf16_v2_num_pixel_tiles(p.N, p.H, p.W, p.Cout)) {
-    set_error("conv3x3_fwd: the <%d,%d,%d> tiling writes %d statistics slab rows, mau_conv3x3_num_pixel_tiles reports %d", BN, MT, NW,
-              G::WM * nPixTiles, conv_bf16_v2_num_pixel_tiles(p.N, p.H, p.W, p.Cout));
-    return MAU_ERR_ARG;
-  }
-  const int nCt = p.CoutPad / BN;
-  // fewer pixel tiles than XCDs (single-tile inference at the deep levels): "every XCD owns a range of pixel tiles" would leave XCDs
-  // without work -- the items go out in plain order instead (item I = (pixel tile I / nCt, cout tile I % nCt) on XCD I % 8)
-  const bool spread = nPixTiles < ds.xcds;
-  const int xcds = spread ? 1 : ds.xcds;
-  q.xcdShift = spread ? 0 : ds.xcd_shift;
-  const int nItems = round_up(nPixTiles, xcds) * nCt;
-  // persistent: as many workgroups as fit the chip at once
-  const int per_cu = (int)((160 * 1024) / G::LDS) >= 2 && NW == 4 ? 2 : 1;
-  // (launch_cus(): the device's CUs, or the calling thread's budget -- mau_set_cu_budget)
-  int grid = launch_cus() / ds.xcds * ds.xcds * per_cu;      // a multiple of the XCD count, like nItems: a workgroup stays on its XCD's slice
-  if (grid > nItems) grid = nItems;
-  // the 16x16x32 loop walks stages in pairs: big-tile variants, buffer-addressed loader, an even number of stages
-  // (MAU_CONV_M16=0: the 32x32x16 loop everywhere -- the exact big-tile tests run both loops on the production tilings)
-  static const bool m16 = getenv("MAU_CONV_M16") == nullptr || atoi(getenv("MAU_CONV_M16")) != 0;
-  bool done = false;
-  // MaxPool2d(2,2) of the activation (inference, one tensor source): written by the epilogue from the registers it stores; anything else
-  // runs the convolution as it is and mau_maxpool2x2_fwd behind it (same bits)
-  const bool pool_behind = q.pool != nullptr && !(EPI == EPI_POST && p.C1 == 0 && p.E == 0);
-  if (pool_behind) q.pool = nullptr;
-  if constexpr (MT == 4) {
-    if (m16 && q.fast && q.nChunks % 2 == 0) {
-      if (p.C1 == 0 && p.E == 0)
-        MAU_LAUNCH((conv3x3_bf16_kernel<BN, MT, NW, EPI, F16, true, true, true>), dim3(grid), dim3(NW * 64), G::LDS, st, q, nPixTiles, nCt, nItems);
-      else
-        MAU_LAUNCH((conv3x3_bf16_kernel<BN, MT, NW, EPI, F16, true, true>), dim3(grid), dim3(NW * 64), G::LDS, st, q, nPixTiles, nCt, nItems);
-      done = true;
-    }
-  }
-  if constexpr (HAS_KG) {
-    // Two K groups per workgroup where the layer leaves every CU at most ONE 4-wave workgroup (single-tile inference at the deep
-    // levels, VERDICT r4 #6): the stages are dealt to two wave groups, a wave's chain of dependent MFMA groups halves and each SIMD
-    // holds two waves.  Even stage counts only (same barriers in both groups); MAU_CONV_KG=0 switches it off (A/B).
-    if (!done && q.fast && k_groups_rule(q.nChunks, nItems)) {
-      MAU_LAUNCH((conv3x3_bf16_kernel<BN, MT, NW, EPI, F16, true, false, false, 2>), dim3(nItems), dim3(NW * 2 * 64), 2 * G::LDS, st, q, nPixTiles, nCt, nItems);
-      done = true;
-    }
-  }
-  if (done) {
-  } else if (q.fast) {
-    MAU_LAUNCH((conv3x3_bf16_kernel<BN, MT, NW, EPI, F16, true, false>), dim3(grid), dim3(NW * 64), G::LDS, st, q, nPixTiles, nCt, nItems);
-  } else {
-    MAU_LAUNCH((conv3x3_bf16_kernel<BN, MT, NW, EPI, F16, false, false>), dim3(grid), dim3(NW * 64), G::LDS, st, q, nPixTiles, nCt, nItems);
-  }
-  const int rc = check_launch("conv3x3_bf16_kernel");
-  if (rc != MAU_OK || !pool_behind) return rc;
-  return mau_maxpool2x2_fwd(p.y, p.ldy, p.pool, p.ldpool, F16 ? MAU_F16 : MAU_BF16, p.N, p.H, p.W, p.Cout, (mau_stream_t)st);
-}
-
 // Variant choice.  Taller workgroup tiles move fewer LDS-DMA bytes and issue fewer ds_reads per MFMA (measured
 // +5..9 % on full grids), but quarter the number of work items: a layer whose items do not fill the 256 CUs (or that
 // wastes tile rows on a small image) is better off with 16-row tiles.  Score = grid-fill x tile-fill x variant bonus.
 // (Measured and dropped: <64,4,4> = two 4-wave workgroups per CU drifting apart -- the extra weight-slab DMA traffic cost
 //  more than the overlap gained, 207 vs 182 us on the 64->64 level-0 layer; <*,8,4> = one wave per SIMD with 256
 //  accumulators in AGPRs, 0.48 instead of 0.75 fragment reads per MFMA -- 10-90 % slower, nothing hides its epilogue.)
-struct Variant {
-  int th, nw, bn;                  // tile rows, waves per workgroup, output channels per workgroup   ((32, 4, 64) = <64,4,4>; (32, 8, 64) = <64,2,8>; (32, 8, 128) = <128,4,8>)
-};
-static inline Variant pick_variant(int CoutPad, int N, int H, int W, int Cin) {
+static inline TilingId pick_variant(int CoutPad, int N, int H, int W, int Cin) {
   const bool wide = CoutPad % 128 == 0;
   // A 128-multiple layer whose 16-row items would keep fewer than half of the CUs busy (single-tile inference at the deep levels:
   // 512 x 512, B = 1 gives 32 items of <128,2,8> at 32 x 32 pixels) runs on the 64-channel workgroups instead: twice the items of
@@ -1199,11 +1125,11 @@ static inline Variant pick_variant(int CoutPad, int N, int H, int W, int Cin) {
   if (wide) {
     const long tiles16 = (long)N * ceil_div(H, 16) * ceil_div(W, TW);
     // (... and 8-row tiles <64,1,4> while even those items are fewer than half of the CUs: the chain of one wave halves again)
-    if (tiles16 * (CoutPad / 64) * 2 <= device_shape().cus) return {8, 4, 64};        // <64,1,4>
-    if (tiles16 * (CoutPad / 128) * 2 <= device_shape().cus) return {16, 4, 64};      // <64,2,4>
+    if (tiles16 * (CoutPad / 64) * 2 <= device_shape().cus) return T64_1_4;
+    if (tiles16 * (CoutPad / 128) * 2 <= device_shape().cus) return T64_2_4;
   }
   const int nCt = CoutPad / (wide ? 128 : 64);
-  Variant best = {16, wide ? 8 : 4, wide ? 128 : 64};
+  TilingId best = wide ? T128_2_8 : T64_2_4;
   double best_score = -1.0;
   // 64-row tiles exist for the 64-wide variant only (<64,4,8>: the per-MFMA LDS-read and DMA ratios of <128,4,8>)
   for (int th = 16; th <= (wide ? 32 : 64); th *= 2) {
@@ -1216,7 +1142,7 @@ static inline Variant pick_variant(int CoutPad, int N, int H, int W, int Cin) {
     const double score = grid_fill * tile_fill * (th == 64 ? 1.10 : th == 32 ? 1.06 : 1.0);
     if (score > best_score) {
       best_score = score;
-      best = {th, nw, wide ? 128 : 64};
+      best = wide ? (th == 32 ? T128_4_8 : T128_2_8) : (th == 64 ? T64_4_8 : th == 32 ? T64_2_8 : T64_2_4);
     }
   }
   // Level 0 (64 output channels, the 64-row tile wins the score): TWO independent 4-wave workgroups per CU, each on a 32 x 16 pixel
@@ -1230,65 +1156,188 @@ static inline Variant pick_variant(int CoutPad, int N, int H, int W, int Cin) {
   // The statistics slab is sized by conv_bf16_v2_num_pixel_tiles, which does not know Cin (Cin = 0: unknown, the slab-geometry
   // query) and so counts the rows of <64,4,4>: 4 * ceil(H/32) per tile column and image.  <64,4,8> writes 8 * ceil(H/64), which is the
   // same number only while ceil(H/32) is even -- the K rule applies to those heights alone (H = 256, 250: the measured ones); at any
-  // other height <64,4,4> runs whatever Cin is.  v2::launch refuses a slab whose row count differs from the query's.
+  // other height <64,4,4> runs whatever Cin is.  launch_conv_bf16_v2 refuses a slab whose row count differs from the query's.
   static const int l0 = getenv("MAU_CONV_L0") ? atoi(getenv("MAU_CONV_L0")) : -1;      // test hook: 0 / 1 force <64,4,8> / <64,4,4> in the query and the launch alike (both forms stay under the exact big-tile tests)
-  if (!wide && best.th == 64 && (l0 < 0 ? Cin <= 192 || ceil_div(H, 32) % 2 != 0 : l0 != 0)) best = {32, 4, 64};
+  if (!wide && best == T64_4_8 && (l0 < 0 ? Cin <= 192 || ceil_div(H, 32) % 2 != 0 : l0 != 0)) best = T64_4_4;
   return best;
+}
+
+// ---- The launch plan of one layer: everything the host decides, decided once.  The size queries read it, launch<> executes it. ----
+enum LoopForm {
+  LOOP_GENERAL,      // 32x32x16 loop, 64-bit select-only loader (channel counts off the 16-channel grid)
+  LOOP_FAST,         // 32x32x16 loop, buffer-addressed loader
+  LOOP_PAIR,         // 16x16x32 stage-pair loop (M16)
+  LOOP_PAIR_ONE,     // ... reading one tensor (ONE)
+  LOOP_KGROUPS       // 32x32x16 loop, two K groups per workgroup (KG = 2)
+};
+struct ConvPlan {
+  int tiling;                                // index into kTilings
+  int tilesX, tilesY, nChunks, nPixTiles;
+  int slabRows;                              // rows of the BatchNorm partial-sum slab: one per (pixel tile, wave row of the workgroup)
+  int nCt, nItems, xcdShift;
+  int per_cu, grid;
+  int form;                                  // LoopForm
+};
+// Cin = 0: input channels unknown (the slab-geometry query).  fast: every 16-channel stage lies inside one tensor (loader_is_fast);
+// one_source: no second tensor, no broadcast embedding.
+static inline ConvPlan make_plan(int N, int H, int W, int Cin, int CoutPad, int epi, bool fast, bool one_source) {
+  const DeviceShape ds = device_shape();
+  ConvPlan pl;
+  pl.tiling = pick_variant(CoutPad, N, H, W, Cin);
+  const Tiling& t = kTilings[pl.tiling];
+  pl.tilesX = ceil_div(W, TW);
+  pl.tilesY = ceil_div(H, t.th);
+  pl.nChunks = ceil_div(Cin, KC);
+  pl.nPixTiles = N * pl.tilesX * pl.tilesY;
+  pl.slabRows = t.wm * pl.nPixTiles;
+  pl.nCt = CoutPad / t.bn;
+  // fewer pixel tiles than XCDs (single-tile inference at the deep levels): "every XCD owns a range of pixel tiles" would leave XCDs
+  // without work -- the items go out in plain order instead (item I = (pixel tile I / nCt, cout tile I % nCt) on XCD I % 8)
+  const bool spread = pl.nPixTiles < ds.xcds;
+  pl.xcdShift = spread ? 0 : ds.xcd_shift;
+  pl.nItems = round_up(pl.nPixTiles, spread ? 1 : ds.xcds) * pl.nCt;
+  // persistent: as many workgroups as fit the chip at once
+  pl.per_cu = (int)((160 * 1024) / t.lds) >= 2 && t.nw == 4 ? 2 : 1;
+  // (launch_cus(): the device's CUs, or the calling thread's budget -- mau_set_cu_budget)
+  pl.grid = launch_cus() / ds.xcds * ds.xcds * pl.per_cu;      // a multiple of the XCD count, like nItems: a workgroup stays on its XCD's slice
+  if (pl.grid > pl.nItems) pl.grid = pl.nItems;
+  // the 16x16x32 loop walks stages in pairs: big-tile variants, buffer-addressed loader, an even number of stages
+  // (MAU_CONV_M16=0: the 32x32x16 loop everywhere -- the exact big-tile tests run both loops on the production tilings)
+  static const bool m16 = getenv("MAU_CONV_M16") == nullptr || atoi(getenv("MAU_CONV_M16")) != 0;
+  if (t.mt == 4 && m16 && fast && pl.nChunks % 2 == 0) {
+    pl.form = one_source ? LOOP_PAIR_ONE : LOOP_PAIR;
+  } else if (has_k_groups(t.bn, t.mt, t.nw) && epi != EPI_STATS && fast && k_groups_rule(pl.nChunks, pl.nItems)) {
+    // Two K groups per workgroup where the layer leaves every CU at most ONE 4-wave workgroup (single-tile inference at the deep
+    // levels, VERDICT r4 #6): the stages are dealt to two wave groups, a wave's chain of dependent MFMA groups halves and each SIMD
+    // holds two waves.  Even stage counts only (same barriers in both groups); MAU_CONV_KG=0 switches it off (A/B).
+    pl.form = LOOP_KGROUPS;
+    pl.grid = pl.nItems;                     // (not persistent: one workgroup per item)
+  } else {
+    pl.form = fast ? LOOP_FAST : LOOP_GENERAL;
+  }
+  return pl;
+}
+
+// Executes a plan: LDS attributes, the plan's tile fields into ConvP, the one launch its form names.
+template <int BN, int MT, int NW, int EPI, bool F16>
+static int launch(const ConvP& p, const ConvPlan& pl, hipStream_t st) {
+  using G = Geo<BN, MT, NW>;
+  MAU_LDS_ATTR(G::LDS, &conv3x3_bf16_kernel<BN, MT, NW, EPI, F16, true, false>);
+  MAU_LDS_ATTR(G::LDS, &conv3x3_bf16_kernel<BN, MT, NW, EPI, F16, false, false>);
+  if constexpr (MT == 4) {
+    MAU_LDS_ATTR(G::LDS, &conv3x3_bf16_kernel<BN, MT, NW, EPI, F16, true, true>);
+    MAU_LDS_ATTR(G::LDS, (&conv3x3_bf16_kernel<BN, MT, NW, EPI, F16, true, true, true>));
+  }
+  constexpr bool HAS_KG = has_k_groups(BN, MT, NW) && EPI != EPI_STATS;       // the under-filled-layer forms <64,1,4> / <64,2,4>
+  if constexpr (HAS_KG) MAU_LDS_ATTR(2 * G::LDS, (&conv3x3_bf16_kernel<BN, MT, NW, EPI, F16, true, false, false, 2>));
+  ConvP q = p;
+  q.tilesX = pl.tilesX;
+  q.tilesY = pl.tilesY;
+  q.nChunks = pl.nChunks;
+  q.xcdShift = pl.xcdShift;
+  q.fast = pl.form != LOOP_GENERAL ? 1 : 0;
+  // MaxPool2d(2,2) of the activation (inference, one tensor source): written by the epilogue from the registers it stores; anything else
+  // runs the convolution as it is and mau_maxpool2x2_fwd behind it (same bits)
+  const bool pool_behind = q.pool != nullptr && !(EPI == EPI_POST && p.C1 == 0 && p.E == 0);
+  if (pool_behind) q.pool = nullptr;
+  const dim3 grid(pl.grid), block(NW * 64);
+  bool launched = false;
+  switch (pl.form) {
+    case LOOP_PAIR_ONE:
+      if constexpr (MT == 4) {
+        MAU_LAUNCH((conv3x3_bf16_kernel<BN, MT, NW, EPI, F16, true, true, true>), grid, block, G::LDS, st, q, pl.nPixTiles, pl.nCt, pl.nItems);
+        launched = true;
+      }
+      break;
+    case LOOP_PAIR:
+      if constexpr (MT == 4) {
+        MAU_LAUNCH((conv3x3_bf16_kernel<BN, MT, NW, EPI, F16, true, true>), grid, block, G::LDS, st, q, pl.nPixTiles, pl.nCt, pl.nItems);
+        launched = true;
+      }
+      break;
+    case LOOP_KGROUPS:
+      if constexpr (HAS_KG) {
+        MAU_LAUNCH((conv3x3_bf16_kernel<BN, MT, NW, EPI, F16, true, false, false, 2>), grid, dim3(NW * 2 * 64), 2 * G::LDS, st, q, pl.nPixTiles, pl.nCt, pl.nItems);
+        launched = true;
+      }
+      break;
+    case LOOP_FAST:
+      MAU_LAUNCH((conv3x3_bf16_kernel<BN, MT, NW, EPI, F16, true, false>), grid, block, G::LDS, st, q, pl.nPixTiles, pl.nCt, pl.nItems);
+      launched = true;
+      break;
+    case LOOP_GENERAL:
+      MAU_LAUNCH((conv3x3_bf16_kernel<BN, MT, NW, EPI, F16, false, false>), grid, block, G::LDS, st, q, pl.nPixTiles, pl.nCt, pl.nItems);
+      launched = true;
+      break;
+  }
+  if (!launched) {
+    set_error("conv3x3_fwd: the <%d,%d,%d> tiling has no loop form %d (epilogue %d)", BN, MT, NW, pl.form, EPI);
+    return MAU_ERR_ARG;
+  }
+  const int rc = check_launch("conv3x3_bf16_kernel");
+  if (rc != MAU_OK || !pool_behind) return rc;
+  return mau_maxpool2x2_fwd(p.y, p.ldy, p.pool, p.ldpool, F16 ? MAU_F16 : MAU_BF16, p.N, p.H, p.W, p.Cout, (mau_stream_t)st);
 }
 }  // namespace v2
 
 // ---- translation units ----
 // The kernel has 120 instantiations (7 tile variants x 2 loaders + 3 big-tile variants x 2 stage-pair forms, x 3 epilogues x 2 operand types) of
 // 4-5 s each: one (epilogue, operand type) slice per translation unit (conv3x3_bf16_e<EPI>_<type>.hip define MAU_CONV_TU_EPI /
-// MAU_CONV_TU_F16 and include this file), built in parallel; this file alone carries the variant choice and the dispatcher.
+// MAU_CONV_TU_F16 and include this file), built in parallel; this file alone builds plans (the size queries and launch_conv_bf16_v2); a slice only executes one.
 #define MAU_CONV_TU_NAME2(e, f) launch_conv_bf16_tu_e##e##_f##f
 #define MAU_CONV_TU_NAME(e, f) MAU_CONV_TU_NAME2(e, f)
 #ifdef MAU_CONV_TU_EPI
-int MAU_CONV_TU_NAME(MAU_CONV_TU_EPI, MAU_CONV_TU_F16)(const ConvP& p, int th, int nw, int bn, hipStream_t st) {
+int MAU_CONV_TU_NAME(MAU_CONV_TU_EPI, MAU_CONV_TU_F16)(const ConvP& p, const v2::ConvPlan& pl, hipStream_t st) {
   constexpr int E = MAU_CONV_TU_EPI;
   constexpr bool F = MAU_CONV_TU_F16 != 0;
-  if (bn == 128) return th == 32 ? v2::launch<128, 4, 8, E, F>(p, st) : v2::launch<128, 2, 8, E, F>(p, st);
-  if (th == 8) return v2::launch<64, 1, 4, E, F>(p, st);
-  if (th == 64) return v2::launch<64, 4, 8, E, F>(p, st);
-  if (th == 32 && nw == 4) return v2::launch<64, 4, 4, E, F>(p, st);
-  return th == 32 ? v2::launch<64, 2, 8, E, F>(p, st) : v2::launch<64, 2, 4, E, F>(p, st);
+  switch (pl.tiling) {
+    case v2::T128_4_8: return v2::launch<128, 4, 8, E, F>(p, pl, st);
+    case v2::T128_2_8: return v2::launch<128, 2, 8, E, F>(p, pl, st);
+    case v2::T64_1_4: return v2::launch<64, 1, 4, E, F>(p, pl, st);
+    case v2::T64_2_4: return v2::launch<64, 2, 4, E, F>(p, pl, st);
+    case v2::T64_4_4: return v2::launch<64, 4, 4, E, F>(p, pl, st);
+    case v2::T64_2_8: return v2::launch<64, 2, 8, E, F>(p, pl, st);
+    case v2::T64_4_8: return v2::launch<64, 4, 8, E, F>(p, pl, st);
+  }
+  set_error("conv3x3_fwd: no tiling %d", pl.tiling);
+  return MAU_ERR_ARG;
 }
 #else
-int launch_conv_bf16_tu_e0_f0(const ConvP&, int, int, int, hipStream_t);
-int launch_conv_bf16_tu_e1_f0(const ConvP&, int, int, int, hipStream_t);
-int launch_conv_bf16_tu_e2_f0(const ConvP&, int, int, int, hipStream_t);
-int launch_conv_bf16_tu_e0_f1(const ConvP&, int, int, int, hipStream_t);
-int launch_conv_bf16_tu_e1_f1(const ConvP&, int, int, int, hipStream_t);
-int launch_conv_bf16_tu_e2_f1(const ConvP&, int, int, int, hipStream_t);
+int launch_conv_bf16_tu_e0_f0(const ConvP&, const v2::ConvPlan&, hipStream_t);
+int launch_conv_bf16_tu_e1_f0(const ConvP&, const v2::ConvPlan&, hipStream_t);
+int launch_conv_bf16_tu_e2_f0(const ConvP&, const v2::ConvPlan&, hipStream_t);
+int launch_conv_bf16_tu_e0_f1(const ConvP&, const v2::ConvPlan&, hipStream_t);
+int launch_conv_bf16_tu_e1_f1(const ConvP&, const v2::ConvPlan&, hipStream_t);
+int launch_conv_bf16_tu_e2_f1(const ConvP&, const v2::ConvPlan&, hipStream_t);
 
-// rows of the BatchNorm partial-sum slab: one per (pixel tile, wave row of the workgroup)
-int conv_bf16_v2_num_pixel_tiles(int N, int H, int W, int Cout) {
-  const int CoutPad = round_up(Cout, 64);
-  const v2::Variant v = v2::pick_variant(CoutPad, N, H, W, 0);     // (the slab geometry must not depend on Cin: see pick_variant's level-0 rule)
-  const int th = v.th;
-  const int wm = (v.bn == 64 && v.nw == 8) ? v2::Geo<64, 2, 8>::WM : 4;    // <128,*,8>, <64,2,4>, <64,4,4>: 4 wave rows; <64,2,8>, <64,4,8>: 8
-  static_assert(v2::Geo<64, 4, 4>::WM == 4 && v2::Geo<64, 4, 4>::TH == 32, "slab rows");
-  static_assert(v2::Geo<64, 2, 8>::WM == 8 && v2::Geo<64, 4, 8>::WM == 8 && v2::Geo<64, 4, 8>::TH == 64, "slab rows");
-  static_assert(v2::Geo<128, 2, 8>::WM == 4 && v2::Geo<128, 4, 8>::WM == 4 && v2::Geo<64, 2, 4>::WM == 4, "slab rows");
-  static_assert(v2::Geo<64, 1, 4>::WM == 4 && v2::Geo<64, 1, 4>::TH == 8, "slab rows");
-  return wm * N * ceil_div(H, th) * ceil_div(W, v2::TW);
-}
+// rows of the BatchNorm partial-sum slab.  The query does not see the layer's input channels (Cin = 0), so the slab geometry must
+// not depend on them: see pick_variant's level-0 rule
+static int slab_rows_without_cin(int N, int H, int W, int CoutPad) { return v2::make_plan(N, H, W, 0, CoutPad, v2::EPI_STATS, false, true).slabRows; }
+int conv_bf16_v2_num_pixel_tiles(int N, int H, int W, int Cout) { return slab_rows_without_cin(N, H, W, round_up(Cout, 64)); }
 
 // which tile variant the 16-bit kernel runs for a layer: tile rows, waves per workgroup, output channels per workgroup
 // ... and, given the layer's input channels (a single-source layer on the buffer-addressed loader, plain or inference epilogue),
 // the number of K groups per workgroup (2 = the under-filled-layer form, see k_groups_rule)
 void conv_bf16_v2_variant(int N, int H, int W, int Cin, int Cout, int* th, int* nw, int* bn, int* kg) {
-  const int CoutPad = round_up(Cout, 64);
-  const v2::Variant v = v2::pick_variant(CoutPad, N, H, W, Cin);
-  *th = v.th;
-  *nw = v.nw;
-  *bn = v.bn;
-  const int mt = v.th / (2 * (v.nw / (v.bn / 64)));
-  const DeviceShape ds = device_shape();
-  const int nPixTiles = N * ceil_div(H, v.th) * ceil_div(W, v2::TW);
-  const int nItems = round_up(nPixTiles, nPixTiles < ds.xcds ? 1 : ds.xcds) * (CoutPad / v.bn);
-  const bool m16 = mt == 4 && Cin > 0 && ceil_div(Cin, v2::KC) % 2 == 0;
-  *kg = (Cin > 0 && Cin % v2::KC == 0 && !m16 && v2::has_k_groups(v.bn, mt, v.nw) && v2::k_groups_rule(ceil_div(Cin, v2::KC), nItems)) ? 2 : 1;
+  // (a dense single tensor is on the buffer-addressed loader when its channels fill whole 16-channel stages)
+  const v2::ConvPlan pl = v2::make_plan(N, H, W, Cin, round_up(Cout, 64), v2::EPI_PLAIN, Cin > 0 && Cin % v2::KC == 0, true);
+  const v2::Tiling& t = v2::kTilings[pl.tiling];
+  *th = t.th;
+  *nw = t.nw;
+  *bn = t.bn;
+  *kg = pl.form == v2::LOOP_KGROUPS ? 2 : 1;
+}
+
+// buffer-addressed halo loads: every 16-channel stage inside one tensor's (zero-padded) pixel row, 31-bit byte offsets
+static bool loader_is_fast(const ConvP& p) {
+  const int KC = v2::KC;
+  const long long px = (long long)p.N * p.H * p.W;
+  // (with a broadcast embedding behind the tensors: the tensors end on a stage boundary and the embedding fills whole stages;
+  //  the lane offset of an embedding stage is derived from the source-0 offset: its 16-byte-half bit needs 2 * ldx % 32 == 0)
+  const bool emb_ok = p.E == 0 || (p.emb_lp != nullptr && p.E % KC == 0 && (p.C0 + p.C1) % KC == 0 && p.ldx % KC == 0);
+  const bool one = p.C1 == 0 && p.ldx % KC == 0 && round_up(p.C0, KC) <= p.ldx;
+  const bool two = p.C1 > 0 && p.C0 % KC == 0 && p.C0 <= p.ldx && round_up(p.C1, KC) <= p.ldx1;
+  return emb_ok && (one || two) && px * p.ldx * 2 < (1ll << 31) && px * p.ldx1 * 2 < (1ll << 31);
 }
 
 int launch_conv_bf16_v2(const ConvP& p, bool f16, hipStream_t st) {
@@ -1297,11 +1346,25 @@ int launch_conv_bf16_v2(const ConvP& p, bool f16, hipStream_t st) {
     return MAU_ERR_ARG;
   }
   static_assert(v2::EPI_PLAIN == 0 && v2::EPI_STATS == 1 && v2::EPI_POST == 2, "translation-unit names");
-  const v2::Variant v = v2::pick_variant(p.CoutPad, p.N, p.H, p.W, p.C0 + p.C1 + p.E);
-  const int th = v.th, nw = v.nw, bn = v.bn;
-  if (p.post_scale != nullptr) return f16 ? launch_conv_bf16_tu_e2_f1(p, th, nw, bn, st) : launch_conv_bf16_tu_e2_f0(p, th, nw, bn, st);   // (a post-affine launch carries no slab)
-  if (p.slab != nullptr) return f16 ? launch_conv_bf16_tu_e1_f1(p, th, nw, bn, st) : launch_conv_bf16_tu_e1_f0(p, th, nw, bn, st);
-  return f16 ? launch_conv_bf16_tu_e0_f1(p, th, nw, bn, st) : launch_conv_bf16_tu_e0_f0(p, th, nw, bn, st);
+  const int epi = p.post_scale != nullptr ? v2::EPI_POST : p.slab != nullptr ? v2::EPI_STATS : v2::EPI_PLAIN;   // (a post-affine launch carries no slab)
+  const v2::ConvPlan pl = v2::make_plan(p.N, p.H, p.W, p.C0 + p.C1 + p.E, p.CoutPad, epi, loader_is_fast(p), p.C1 == 0 && p.E == 0);
+  if ((long long)pl.nChunks * 9 * p.CoutPad * v2::KC * 2 >= (1ll << 31)) {
+    set_error("conv3x3_fwd: packed weights beyond 2 GiB");
+    return MAU_ERR_ARG;
+  }
+  // the caller sized the statistics slab by the query, the kernel writes one row per (pixel tile, wave row): a variant rule that lets
+  // the two drift apart must not reach the device
+  if (p.slab != nullptr && pl.slabRows != slab_rows_without_cin(p.N, p.H, p.W, p.CoutPad)) {
+    const v2::Tiling& t = v2::kTilings[pl.tiling];
+    set_error("conv3x3_fwd: the <%d,%d,%d> tiling writes %d statistics slab rows, mau_conv3x3_num_pixel_tiles reports %d", t.bn, t.mt, t.nw,
+              pl.slabRows, slab_rows_without_cin(p.N, p.H, p.W, p.CoutPad));
+    return MAU_ERR_ARG;
+  }
+  switch (epi) {
+    case v2::EPI_POST: return f16 ? launch_conv_bf16_tu_e2_f1(p, pl, st) : launch_conv_bf16_tu_e2_f0(p, pl, st);
+    case v2::EPI_STATS: return f16 ? launch_conv_bf16_tu_e1_f1(p, pl, st) : launch_conv_bf16_tu_e1_f0(p, pl, st);
+    default: return f16 ? launch_conv_bf16_tu_e0_f1(p, pl, st) : launch_conv_bf16_tu_e0_f0(p, pl, st);
+  }
 }
 #endif
 

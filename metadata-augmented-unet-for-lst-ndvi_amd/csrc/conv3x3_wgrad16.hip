@@ -408,30 +408,26 @@ __global__ __launch_bounds__((BCO / 64) * 4 * KG * 64) void wgrad16_kernel(Wgrad
 }
 
 template <int BCO, int KG, bool F16, bool MIXED>
-static int launch(const WgradP& p, int nsplit, int xcd_shift, hipStream_t st) {
+static int launch(const WgradP& p, const WgPlan& pl, hipStream_t st) {
   constexpr int NW = (BCO / 64) * 4 * KG;
   constexpr size_t stage = (size_t)(TH * TW * BCO * 2) + X_BYTES;
   constexpr size_t red = KG == 2 ? (size_t)(NW / 2) * 3 * 16 * 64 * sizeof(float) : 0;
   constexpr size_t lds = 2 * stage > red ? 2 * stage : red;
   static_assert(lds <= 160 * 1024, "LDS budget");
   MAU_LDS_ATTR(lds, &wgrad16_kernel<BCO, KG, F16, MIXED>);
-  const int total = nsplit * (p.CoutPad / BCO) * (p.CinPad / BCI);
-  // (xcd_shift < 0: a whole number of workgroups per XCD; the surplus ones return at once -- conv3x3_wgrad_bf16.hip wgrad_grid)
-  dim3 grid(xcd_shift < 0 ? (((total + (1 << -xcd_shift) - 1) >> -xcd_shift) << -xcd_shift) : total);
-  MAU_LAUNCH((wgrad16_kernel<BCO, KG, F16, MIXED>), grid, dim3(NW * 64), lds, st, p, nsplit, xcd_shift);
+  MAU_LAUNCH((wgrad16_kernel<BCO, KG, F16, MIXED>), dim3(pl.grid), dim3(NW * 64), lds, st, p, pl.nsplit, pl.xcd_shift);
   return check_launch("wgrad16_kernel");
 }
 }  // namespace wg3
 
 template <bool F16>
-static int launch16(const WgradP& q, bool mixed, int nsplit, int xcd_shift, hipStream_t st) {
-  if (q.CoutPad % 128 == 0) return mixed ? wg3::launch<128, 1, F16, true>(q, nsplit, xcd_shift, st) : wg3::launch<128, 1, F16, false>(q, nsplit, xcd_shift, st);
-  return mixed ? wg3::launch<64, 2, F16, true>(q, nsplit, xcd_shift, st) : wg3::launch<64, 2, F16, false>(q, nsplit, xcd_shift, st);
+static int launch16(const WgradP& q, const WgPlan& pl, hipStream_t st) {
+  if (pl.bco == 128) return pl.mixed ? wg3::launch<128, 1, F16, true>(q, pl, st) : wg3::launch<128, 1, F16, false>(q, pl, st);
+  return pl.mixed ? wg3::launch<64, 2, F16, true>(q, pl, st) : wg3::launch<64, 2, F16, false>(q, pl, st);
 }
 
-// mixed: some 64-channel block of input channels straddles two sources
-int launch_wgrad16(const WgradP& q, bool f16, bool mixed, int nsplit, int xcd_shift, hipStream_t st) {
-  return f16 ? launch16<true>(q, mixed, nsplit, xcd_shift, st) : launch16<false>(q, mixed, nsplit, xcd_shift, st);
+int launch_wgrad16(const WgradP& q, bool f16, const WgPlan& pl, hipStream_t st) {
+  return f16 ? launch16<true>(q, pl, st) : launch16<false>(q, pl, st);
 }
 
 }  // namespace mau

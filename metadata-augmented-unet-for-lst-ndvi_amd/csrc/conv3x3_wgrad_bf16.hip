@@ -369,8 +369,7 @@ __global__ __launch_bounds__(BCO * 4 * KG) void wgrad_bf16_kernel(WgradP p, int 
 //         up to a whole number of workgroups per XCD and the surplus ones return at once;
 //     0 : a device with one XCD: plain order id = split + nsplit * tile.
 // Either way the workgroups of one split -- which stream the SAME pixels -- are resident on one XCD at about the same time.
-static inline bool wgrad_xcd_order() { return true; }
-static inline int wgrad_xcd_shift(int nsplit, int tilesOut) {
+static inline int wgrad_xcd_shift(int nsplit) {
   const DeviceShape ds = device_shape();
   if (ds.xcds <= 1) return 0;
   return nsplit % ds.xcds == 0 ? ds.xcd_shift : -ds.xcd_shift;
@@ -381,7 +380,7 @@ static inline int wgrad_grid(int nsplit, int tilesOut, int xcd_shift) {
 }
 
 template <int BCO, int KG, bool F16, int NS>
-static int launch(const WgradP& p, int nsplit, hipStream_t st) {
+static int launch(const WgradP& p, const WgPlan& pl, hipStream_t st) {
   constexpr int NW = BCO / 16 * KG;
   constexpr int DY_Q = TH * TW * (BCO / 8) / 64;
   constexpr int X_Q = (HALO * 8 + 63) / 64;
@@ -391,9 +390,7 @@ static int launch(const WgradP& p, int nsplit, hipStream_t st) {
   constexpr size_t lds = NS * stage > red ? NS * stage : red;
   static_assert(lds <= 160 * 1024, "LDS budget");
   MAU_LDS_ATTR(lds, &wgrad_bf16_kernel<BCO, KG, F16, NS>);
-  const int xcd_shift = wgrad_xcd_shift(nsplit, (p.CoutPad / BCO) * (p.CinPad / BCI));
-  dim3 grid(wgrad_grid(nsplit, (p.CoutPad / BCO) * (p.CinPad / BCI), xcd_shift));
-  MAU_LAUNCH((wgrad_bf16_kernel<BCO, KG, F16, NS>), grid, dim3(BCO * 4 * KG), lds, st, p, nsplit, xcd_shift);
+  MAU_LAUNCH((wgrad_bf16_kernel<BCO, KG, F16, NS>), dim3(pl.grid), dim3(BCO * 4 * KG), lds, st, p, pl.nsplit, pl.xcd_shift);
   return check_launch("wgrad_bf16_kernel");
 }
 }  // namespace wg2
@@ -401,12 +398,11 @@ static int launch(const WgradP& p, int nsplit, hipStream_t st) {
 // Which kernel multiplies a layer: the 16x16x32 kernel (conv3x3_wgrad16.hip) works on 4 x 32 pixel tiles, this file's 32x32x16 kernel on
 // 8 x 16 ones.  The first is ~9 % faster per MFMA (clock), so it takes every layer unless its tiles waste more than that on
 // pixels outside the image (16-pixel-wide bottleneck images: twice the work).  MAU_WGRAD16=0: the 32x32x16 kernel everywhere.
-int launch_wgrad16(const WgradP& q, bool f16, bool mixed, int nsplit, int xcd_shift, hipStream_t st);
 struct WgVariant {
   bool k16;
   int th, tw;
 };
-static WgVariant wgrad_variant(int H, int W, bool addressable = true) {
+static WgVariant wgrad_variant(int H, int W, bool addressable) {
   const char* e = getenv("MAU_WGRAD16");
   const bool allow = addressable && (e == nullptr || atoi(e) != 0);
   const double a16 = (double)ceil_div(H, 4) * 4 * ceil_div(W, 32) * 32, a32 = (double)ceil_div(H, wg2::TH) * wg2::TH * ceil_div(W, wg2::TW) * wg2::TW;
@@ -414,12 +410,8 @@ static WgVariant wgrad_variant(int H, int W, bool addressable = true) {
   return {false, wg2::TH, wg2::TW};
 }
 
-int wgrad_bf16_v2_splits(int N, int H, int W, int Cout, int Cin) {
-  const int CoutPad = round_up(Cout, 64), CinPad = round_up(Cin, 64);
-  const int bco = (CoutPad % 128 == 0) ? 128 : 64;
-  const int outTiles = (CoutPad / bco) * (CinPad / 64);
-  const WgVariant v = wgrad_variant(H, W);
-  const int nTiles = N * ceil_div(H, v.th) * ceil_div(W, v.tw);
+// split count of a layer of nTiles pixel tiles (k16: 4 x 32 ones) and outTiles work items per split
+static int wgrad_splits(int nTiles, bool k16, int CoutPad, int CinPad, int outTiles) {
   // one workgroup per CU is resident (LDS / accumulator budget): pick the split count whose total
   // workgroup count fills whole rounds of the device's CUs, preferring fewer splits (less slab traffic) and
   // at least 4 pixel tiles per workgroup (pipeline fill).
@@ -448,7 +440,7 @@ int wgrad_bf16_v2_splits(int N, int H, int W, int Cout, int Cin) {
   int best = 1;
   double best_cost = 1e300;
   const long cus = launch_cus();
-  const double ov = v.k16 ? 16.0 : 10.0;
+  const double ov = k16 ? 16.0 : 10.0;
   for (int s = 1; s <= smax; ++s) {                // s = workgroups along the split axis = partial slabs
     const long blocks = (long)outTiles * s;
     const long rounds = (blocks + cus - 1) / cus;      // (every split count has an XCD-contiguous work-item order: wgrad_xcd_shift)
@@ -461,27 +453,47 @@ int wgrad_bf16_v2_splits(int N, int H, int W, int Cout, int Cin) {
   return best;
 }
 
+// addressable: the sources fit the 16x16x32 kernel's buffer resources (31-bit byte offsets); the size query has no tensors and
+// assumes they do.  The split count is ALWAYS the addressable variant's, also where the launch falls back to the 8 x 16 kernel:
+// the caller sized the partial-slab workspace from that query.
+static WgPlan make_wg_plan(int N, int H, int W, int Cout, int Cin, bool addressable, bool mixed) {
+  const int CoutPad = round_up(Cout, 64), CinPad = round_up(Cin, 64);
+  const WgVariant vq = wgrad_variant(H, W, true), v = addressable ? vq : wgrad_variant(H, W, false);
+  WgPlan pl;
+  pl.k16 = v.k16;
+  pl.th = v.th;
+  pl.tw = v.tw;
+  pl.bco = (CoutPad % 128 == 0) ? 128 : 64;
+  pl.outTiles = (CoutPad / pl.bco) * (CinPad / 64);
+  pl.tilesX = ceil_div(W, v.tw);
+  pl.tilesY = ceil_div(H, v.th);
+  pl.nTiles = N * pl.tilesX * pl.tilesY;
+  pl.nsplit = wgrad_splits(N * ceil_div(H, vq.th) * ceil_div(W, vq.tw), vq.k16, CoutPad, CinPad, pl.outTiles);
+  pl.xcd_shift = wg2::wgrad_xcd_shift(pl.nsplit);
+  pl.grid = wg2::wgrad_grid(pl.nsplit, pl.outTiles, pl.xcd_shift);
+  pl.mixed = mixed;
+  return pl;
+}
+
+int wgrad_bf16_v2_splits(int N, int H, int W, int Cout, int Cin) { return make_wg_plan(N, H, W, Cout, Cin, true, false).nsplit; }
+
 int launch_wgrad_bf16_v2(const WgradP& p, bool f16, hipStream_t st) {
-  const int nsplit = wgrad_bf16_v2_splits(p.N, p.H, p.W, p.Cout, p.Cin);
   // the 16x16x32 kernel addresses its sources through buffer resources (31-bit byte offsets); a 64-channel block of input channels
   // that straddles two sources (x | x1 | broadcast embedding off the 64-channel grid) takes its MIXED loader
   const long long px = (long long)p.N * p.H * p.W;
   const bool addressable = px * p.ldx * 2 < (1ll << 31) && px * p.ldx1 * 2 < (1ll << 31) && px * p.lddy * 2 < (1ll << 31) && (p.E == 0 || p.emb_lp != nullptr);
   const bool mixed = !((p.C1 == 0 || p.C0 % 64 == 0) && (p.E == 0 || (p.C0 + p.C1) % 64 == 0));
-  const WgVariant v = wgrad_variant(p.H, p.W, addressable);
+  const WgPlan pl = make_wg_plan(p.N, p.H, p.W, p.Cout, p.Cin, addressable, mixed);
   WgradP q = p;
-  q.tilesX = ceil_div(p.W, v.tw);
-  q.tilesY = ceil_div(p.H, v.th);
-  q.nTiles = p.N * q.tilesX * q.tilesY;
-  if (v.k16) {
-    const int bco = p.CoutPad % 128 == 0 ? 128 : 64;
-    return launch_wgrad16(q, f16, mixed, nsplit, wg2::wgrad_xcd_shift(nsplit, (p.CoutPad / bco) * (p.CinPad / 64)), st);
-  }
+  q.tilesX = pl.tilesX;
+  q.tilesY = pl.tilesY;
+  q.nTiles = pl.nTiles;
+  if (pl.k16) return launch_wgrad16(q, f16, pl, st);
 #ifndef WG_NS64
 #define WG_NS64 2
 #endif
-  if (p.CoutPad % 128 == 0) return f16 ? wg2::launch<128, 1, true, 2>(q, nsplit, st) : wg2::launch<128, 1, false, 2>(q, nsplit, st);
-  return f16 ? wg2::launch<64, 2, true, WG_NS64>(q, nsplit, st) : wg2::launch<64, 2, false, WG_NS64>(q, nsplit, st);
+  if (pl.bco == 128) return f16 ? wg2::launch<128, 1, true, 2>(q, pl, st) : wg2::launch<128, 1, false, 2>(q, pl, st);
+  return f16 ? wg2::launch<64, 2, true, WG_NS64>(q, pl, st) : wg2::launch<64, 2, false, WG_NS64>(q, pl, st);
 }
 
 }  // namespace mau

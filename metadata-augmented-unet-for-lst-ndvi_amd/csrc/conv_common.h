@@ -72,7 +72,20 @@ struct PackKC {
 int launch_conv_bf16_v2(const ConvP& p, bool f16, hipStream_t st);   // 16-bit kernels: bf16 or (f16 = true) fp16 operands
 int conv_bf16_v2_num_pixel_tiles(int N, int H, int W, int Cout);
 void conv_bf16_v2_variant(int N, int H, int W, int Cin, int Cout, int* th, int* nw, int* bn, int* kg);
+// The launch plan of one 16-bit weight gradient (make_wg_plan, conv3x3_wgrad_bf16.hip): the split-count query reads it, the
+// launchers of both kernels execute it.
+struct WgPlan {
+  bool k16;             // the 16x16x32 kernel on 4 x 32 pixel tiles (conv3x3_wgrad16.hip), else the 32x32x16 kernel on 8 x 16 ones
+  int th, tw;           // pixel tile
+  int bco;              // output channels per workgroup
+  int outTiles;         // (output-channel block, 64-input-channel block) work items per split
+  int tilesX, tilesY, nTiles;
+  int nsplit;           // partial slabs = workgroups along the split axis
+  int xcd_shift, grid;  // the kernels' work-item order (wgrad_xcd_shift) and the grid that goes with it
+  bool mixed;           // some 64-channel block of input channels straddles two sources
+};
 int launch_wgrad_bf16_v2(const WgradP& p, bool f16, hipStream_t st);      // writes nsplit partial slabs (plain stores)
+int launch_wgrad16(const WgradP& q, bool f16, const WgPlan& pl, hipStream_t st);
 int wgrad_bf16_v2_splits(int N, int H, int W, int Cout, int Cin);
 
 }  // namespace mau

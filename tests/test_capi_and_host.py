@@ -364,7 +364,10 @@ def test_pmc_record_belongs_to_the_library_in_the_tree():
     if not os.path.exists(so):
         pytest.skip("libmau_hip.so not built")
     have = hashlib.sha256(open(so, "rb").read()).hexdigest()
-    recs = sorted(glob.glob(os.path.join(root, "profiles", "r*", "pmc_summary.json")))
+    def rnd(p):
+        return os.path.basename(os.path.dirname(p))[1:]
+    # (newest round by NUMBER, as bench.py's record_rounds(): sorted as text, r10 would come before r9)
+    recs = sorted((p for p in glob.glob(os.path.join(root, "profiles", "r*", "pmc_summary.json")) if rnd(p).isdigit()), key=lambda p: int(rnd(p)))
     assert recs, "no PMC record committed under profiles/"
     latest = json.load(open(recs[-1]))
     assert latest and all("lib_sha256" in v for v in latest.values()), "a PMC record without the library's sha256"

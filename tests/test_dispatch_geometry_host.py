@@ -27,7 +27,7 @@ def _ceil_div(a, b):
 
 
 def _wave_rows(nw, bn):
-    """wave rows of a workgroup = slab rows per pixel tile (the static_asserts of conv_bf16_v2_num_pixel_tiles):
+    """wave rows of a workgroup = slab rows per pixel tile (stated here independently of the library's tiling table, conv3x3_bf16.hip kTilings):
     <64,2,8> and <64,4,8> have 8, every other variant 4"""
     return 8 if (bn == 64 and nw == 8) else 4
 
