@@ -434,6 +434,29 @@ int mau_grad_norm_seg_fill(void* segs_host, int index, const float* ptr, int64_t
 int mau_grad_norm_clip(const void* segs, int nsegs, int total_blocks, double* ws, unsigned* tickets, float max_norm,
                        float* norm_out, float* coef_out, mau_stream_t stream);
 
+/* ---- test-split evaluation metrics (test/evaluate.py:210-275), ONE launch, the maps never leave the device.  Additive to ABI 5 ----
+ * out, tgt (B,C,H,W) fp32 NCHW; cls (B,H,W) uint8 class ids (the land-cover map at t1); scale / shift: C fp64 values each
+ * (NULL = 1 / 0) that un-normalise a channel, p = out * scale[c] + shift[c], g = tgt * scale[c] + shift[c]; ncls in [1,16].
+ * Every value is a double from its load on; products and sums are fp64, not contracted, added in a fixed order: a workgroup
+ * owns a run of image rows of ONE map (mau_eval_metrics_chunks(H, W) workgroups per map, a function of H and W alone), the
+ * workgroup that draws the map's last ticket adds its partials in chunk order -- a row's bits do not depend on B, on the
+ * sample's place in the batch or on the device, and repeat.
+ * rows: (B*C) x mau_eval_metrics_row_elems(ncls) fp64, row b*C + c =
+ *   [0] mean|p-g|  [1] sqrt(mean (p-g)^2)
+ *   [2],[3] population variance of the 5-point Laplacian of p, of g (x[i-1,j] + x[i+1,j] + x[i,j-1] + x[i,j+1] - 4 x[i,j], the
+ *           edge sample repeated beyond the border: scipy.ndimage.laplace's default mode), E[x^2] - E[x]^2 from fp64 sums
+ *   [4],[5] number of non-finite values of out, of tgt   [6],[7] min, max of p   [8],[9] min, max of g  (NaNs skipped)
+ *   [10] number of pixels whose class id is >= ncls (they count toward [0..9] only)
+ *   [11 + k] pixels of class k   [11 + ncls + k] mean|p-g| over them   [11 + 2 ncls + k] sqrt(mean (p-g)^2) over them;
+ *           the two means of a class without pixels are NaN.
+ * ws: fp64 workspace of mau_eval_metrics_ws_elems(B, C, H, W, ncls) elements; tickets: a ZEROED mau_reduce_tickets_elems()
+ * buffer (left zeroed; see mau_reduce_rows_f64).  One launch per mau_reduce_tickets_elems() rows. */
+int mau_eval_metrics_row_elems(int ncls);
+int mau_eval_metrics_chunks(int H, int W);
+size_t mau_eval_metrics_ws_elems(int B, int C, int H, int W, int ncls);
+int mau_eval_metrics(const float* out, const float* tgt, const unsigned char* cls, const double* scale, const double* shift,
+                     double* rows, double* ws, unsigned* tickets, int B, int C, int H, int W, int ncls, mau_stream_t stream);
+
 /* ---- loss: F.mse_loss (src/utils/losses.py:27-39) -------------------------- */
 /* loss[0] = mean((out-tgt)^2) (fp64 accumulation, fixed order); dout (optional) = 2*(out-tgt)/n;
  * partial: fp64 workspace of mau_mse_blocks(n) elements. */

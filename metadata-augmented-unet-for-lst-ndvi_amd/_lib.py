@@ -113,6 +113,10 @@ PROTOTYPES = {
     "mau_emb_fold_fwd": (_i, [_p, _p, _p, _i, _i, _i, _i, _i, _p]),
     "mau_emb_fold_ws_elems": (_sz, [_i, _i, _i]),
     "mau_emb_fold_bwd": (_i, [_p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _p]),
+    "mau_eval_metrics_row_elems": (_i, [_i]),
+    "mau_eval_metrics_chunks": (_i, [_i, _i]),
+    "mau_eval_metrics_ws_elems": (_sz, [_i, _i, _i, _i, _i]),
+    "mau_eval_metrics": (_i, [_p, _p, _p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _p]),
     "mau_mse_blocks": (_i, [_i64]),
     "mau_l1_gradient_blocks": (_i, [_i64]),
     "mau_l1_gradient_loss": (_i, [_p, _p, _p, _p, _p, _f, _f, _i, _i, _i, _i, _p]),

@@ -1,0 +1,196 @@
+// evalmetrics.hip -- per-(sample, channel) error metrics of the test-split evaluation, per land-cover class, in one launch.
+//
+// Everything a row of the reference's test/evaluate.py holds is a sum over the pixels of (prediction, target, class id):
+//   overall MAE / RMSE, MAE / RMSE and pixel count per class, the population variance of the 5-point Laplacian of both
+//   maps (scipy.ndimage.laplace, boundary mode 'reflect': the edge sample repeated), non-finite counts and min / max.
+// Grid (row chunks, (sample, channel) rows): a workgroup owns EVAL_CHUNK_PIX / W (at least one) consecutive image rows of ONE
+// map -- the chunking is a function of (H, W) alone.  Every value becomes a double as it is loaded, p = out * scale + shift
+// and g = tgt * scale + shift are fp64 products and sums without contraction, and every sum is fp64 in a fixed order:
+// a thread adds its pixels in index order, a wave joins its lanes by an xor butterfly (every lane computes the same tree),
+// the four waves are added in wave order, and the workgroup that draws the row's last ticket (last_block_of) adds the
+// row's chunk partials in chunk order and writes the finished row.  A row's bits depend on nothing but its own maps.
+// The class sums are kept in registers: bin k takes `cls == k ? value : 0`, one select per bin and pixel, so that no
+// accumulator is indexed dynamically (fp64 rate is not what limits a kernel that reads 9 bytes per pixel).
+#include <math.h>
+#include "mau_common.h"
+
+#pragma clang fp contract(off)
+
+namespace mau {
+
+constexpr int EVAL_CHUNK_PIX = 4096;     // pixels of a workgroup's run of image rows (250 x 250: 16 rows, 16 chunks per map)
+constexpr int EVAL_MAX_CLS = 16;
+constexpr int EVAL_HEAD = 11;            // row entries in front of the per-class blocks (include/mau_hip.h)
+// per-thread accumulators: 0 sum|d| 1 sum d^2 2,3 sum / sum of squares of lap(p) 4,5 of lap(g) 6,7 non-finite out / tgt
+// 8 min p 9 max p 10 min g 11 max g, then NB counts, NB sums |d|, NB sums d^2 (bin NB-1: class ids >= ncls)
+constexpr int EVAL_ACC0 = 12;
+
+static inline int eval_rows_per_chunk(int W) { return W >= EVAL_CHUNK_PIX ? 1 : EVAL_CHUNK_PIX / W; }
+static inline int eval_chunks(int H, int W) { return ceil_div(H, eval_rows_per_chunk(W)); }
+static inline int eval_bins(int ncls) { return ncls <= 9 ? 10 : EVAL_MAX_CLS + 1; }
+
+__device__ __forceinline__ double eval_join(int v, double a, double b) {
+  return (v == 8 || v == 10) ? fmin(a, b) : (v == 9 || v == 11) ? fmax(a, b) : a + b;
+}
+
+template <int NB>
+__global__ __launch_bounds__(256) void eval_metrics_kernel(const float* __restrict__ out, const float* __restrict__ tgt,
+                                                           const unsigned char* __restrict__ cls, const double* __restrict__ scale,
+                                                           const double* __restrict__ shift, double* part, unsigned* tickets,
+                                                           double* __restrict__ rows, int C, int H, int W, int ncls, int rpc,
+                                                           int row0) {
+  constexpr int NV = EVAL_ACC0 + 3 * NB;
+  __shared__ double wsum[4][NV];
+  __shared__ double tot[NV];
+  const int row = row0 + blockIdx.y, chunks = gridDim.x;
+  const int b = row / C, c = row - b * C;
+  const double sc = scale != nullptr ? scale[c] : 1.0, sh = shift != nullptr ? shift[c] : 0.0;
+  const size_t HW = (size_t)H * W;
+  const float* o = out + (size_t)row * HW;
+  const float* t = tgt + (size_t)row * HW;
+  const unsigned char* k = cls + (size_t)b * HW;
+  const int i0 = blockIdx.x * rpc;
+  const int i1 = i0 + rpc < H ? i0 + rpc : H;
+  const int npx = (i1 - i0) * W;
+
+  double acc[NV];
+#pragma unroll
+  for (int v = 0; v < NV; ++v) acc[v] = 0.0;
+  acc[8] = acc[10] = INFINITY;
+  acc[9] = acc[11] = -INFINITY;
+
+  for (int idx = threadIdx.x; idx < npx; idx += 256) {
+    const int di = idx / W;
+    const int i = i0 + di, j = idx - di * W;
+    const size_t q = (size_t)i * W + j;
+    // the four neighbours with the edge sample repeated (an axis of one pixel contributes x + x - 2x)
+    const size_t qu = i > 0 ? q - W : q, qd = i + 1 < H ? q + W : q;
+    const size_t ql = j > 0 ? q - 1 : q, qr = j + 1 < W ? q + 1 : q;
+    const float of = o[q], tf = t[q];
+    const double p = (double)of * sc + sh, g = (double)tf * sc + sh;
+    const double lp = ((((double)o[qu] * sc + sh) + ((double)o[qd] * sc + sh)) + ((double)o[ql] * sc + sh)) + ((double)o[qr] * sc + sh) - 4.0 * p;
+    const double lg = ((((double)t[qu] * sc + sh) + ((double)t[qd] * sc + sh)) + ((double)t[ql] * sc + sh)) + ((double)t[qr] * sc + sh) - 4.0 * g;
+    const double d = p - g;
+    const double a = fabs(d), d2 = d * d;
+    acc[0] += a;
+    acc[1] += d2;
+    acc[2] += lp;
+    acc[3] += lp * lp;
+    acc[4] += lg;
+    acc[5] += lg * lg;
+    acc[6] += isfinite(of) ? 0.0 : 1.0;
+    acc[7] += isfinite(tf) ? 0.0 : 1.0;
+    acc[8] = fmin(acc[8], p);             // fmin / fmax: a NaN is skipped (it is counted above)
+    acc[9] = fmax(acc[9], p);
+    acc[10] = fmin(acc[10], g);
+    acc[11] = fmax(acc[11], g);
+    const int id = k[q];
+    const int bin = id < ncls ? id : NB - 1;
+#pragma unroll
+    for (int n = 0; n < NB; ++n) {
+      const bool m = bin == n;
+      acc[EVAL_ACC0 + n] += m ? 1.0 : 0.0;
+      acc[EVAL_ACC0 + NB + n] += m ? a : 0.0;
+      acc[EVAL_ACC0 + 2 * NB + n] += m ? d2 : 0.0;
+    }
+  }
+
+  // lanes of a wave: xor butterfly (addition, fmin and fmax commute: every lane ends with the same bits)
+#pragma unroll
+  for (int v = 0; v < NV; ++v) {
+#pragma unroll
+    for (int s = 32; s >= 1; s >>= 1) acc[v] = eval_join(v, acc[v], __shfl_xor(acc[v], s, 64));
+  }
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  if (lane == 0) {
+#pragma unroll
+    for (int v = 0; v < NV; ++v) wsum[wave][v] = acc[v];
+  }
+  __syncthreads();
+  double* prow = part + (size_t)blockIdx.y * chunks * NV;
+  if (threadIdx.x < NV) {
+    const int v = threadIdx.x;
+    double s = wsum[0][v];
+    for (int w = 1; w < 4; ++w) s = eval_join(v, s, wsum[w][v]);
+    prow[(size_t)blockIdx.x * NV + v] = s;
+  }
+  if (!last_block_of(tickets + blockIdx.y, (unsigned)chunks)) return;
+
+  // level 2: the row's chunk partials in chunk order, then the finished row
+  if (threadIdx.x < NV) {
+    const int v = threadIdx.x;
+    double s = prow[v];
+    for (int n = 1; n < chunks; ++n) s = eval_join(v, s, prow[(size_t)n * NV + v]);
+    tot[v] = s;
+  }
+  __syncthreads();
+  const int relems = EVAL_HEAD + 3 * ncls;
+  double* r = rows + (size_t)row * relems;
+  const double n = (double)HW;
+  const int e = threadIdx.x;
+  if (e < relems) {
+    double val;
+    if (e == 0) {
+      val = tot[0] / n;
+    } else if (e == 1) {
+      val = sqrt(tot[1] / n);
+    } else if (e == 2 || e == 3) {           // population variance from the two sums; never below zero
+      const double m = tot[2 * e - 2] / n;
+      val = tot[2 * e - 1] / n - m * m;
+      val = val < 0.0 ? 0.0 : val;
+    } else if (e < 10) {
+      val = tot[e + 2];
+    } else if (e == 10) {
+      val = tot[EVAL_ACC0 + NB - 1];
+    } else {
+      const int blk = (e - EVAL_HEAD) / ncls, kk = (e - EVAL_HEAD) - blk * ncls;
+      const double cnt = tot[EVAL_ACC0 + kk];
+      // an absent class: 0 / 0 = NaN, the host turns it into "no row"
+      val = blk == 0 ? cnt : blk == 1 ? tot[EVAL_ACC0 + NB + kk] / cnt : sqrt(tot[EVAL_ACC0 + 2 * NB + kk] / cnt);
+    }
+    r[e] = val;
+  }
+}
+
+}  // namespace mau
+
+using namespace mau;
+
+extern "C" {
+
+int mau_eval_metrics_row_elems(int ncls) { return ncls >= 1 && ncls <= EVAL_MAX_CLS ? EVAL_HEAD + 3 * ncls : 0; }
+
+int mau_eval_metrics_chunks(int H, int W) { return H > 0 && W > 0 ? eval_chunks(H, W) : 0; }
+
+size_t mau_eval_metrics_ws_elems(int B, int C, int H, int W, int ncls) {
+  if (B <= 0 || C <= 0 || H <= 0 || W <= 0 || ncls < 1 || ncls > EVAL_MAX_CLS) return 0;
+  // the launches of one call reuse the partials of the first mau_reduce_tickets_elems() rows
+  const int64_t nrows = (int64_t)B * C;
+  const int per = mau_reduce_tickets_elems();
+  return (size_t)(nrows < per ? nrows : per) * eval_chunks(H, W) * (EVAL_ACC0 + 3 * eval_bins(ncls));
+}
+
+int mau_eval_metrics(const float* out, const float* tgt, const unsigned char* cls, const double* scale, const double* shift,
+                     double* rows, double* ws, unsigned* tickets, int B, int C, int H, int W, int ncls, mau_stream_t stream) {
+  MAU_REQUIRE(out && tgt && cls && rows && ws && tickets, "eval_metrics: null pointer");
+  MAU_REQUIRE(B > 0 && C > 0 && H > 0 && W > 0, "eval_metrics: non-positive dimension (B %d, C %d, H %d, W %d)", B, C, H, W);
+  MAU_REQUIRE(ncls >= 1 && ncls <= EVAL_MAX_CLS, "eval_metrics: ncls must be in [1,%d], got %d", EVAL_MAX_CLS, ncls);
+  MAU_REQUIRE((int64_t)H * W <= (1 << 30), "eval_metrics: maps of at most 2^30 pixels");
+  MAU_REQUIRE((int64_t)B * C <= (1 << 30), "eval_metrics: at most 2^30 (sample, channel) rows");
+  const int rpc = eval_rows_per_chunk(W), chunks = eval_chunks(H, W);
+  const int nrows = B * C;
+  // one ticket per (sample, channel) row: mau_reduce_tickets_elems() rows per launch
+  const int per = mau_reduce_tickets_elems();
+  for (int row0 = 0; row0 < nrows; row0 += per) {
+    const int nn = nrows - row0 < per ? nrows - row0 : per;
+    if (eval_bins(ncls) == 10)
+      MAU_LAUNCH(eval_metrics_kernel<10>, dim3(chunks, nn), dim3(256), 0, (hipStream_t)stream, out, tgt, cls, scale, shift, ws, tickets, rows, C, H, W, ncls, rpc, row0);
+    else
+      MAU_LAUNCH(eval_metrics_kernel<EVAL_MAX_CLS + 1>, dim3(chunks, nn), dim3(256), 0, (hipStream_t)stream, out, tgt, cls, scale, shift, ws, tickets, rows, C, H, W, ncls, rpc, row0);
+    const int st = check_launch("eval_metrics_kernel");
+    if (st != 0) return st;
+  }
+  return 0;
+}
+
+}  // extern "C"
