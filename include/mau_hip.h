@@ -457,6 +457,47 @@ size_t mau_eval_metrics_ws_elems(int B, int C, int H, int W, int ncls);
 int mau_eval_metrics(const float* out, const float* tgt, const unsigned char* cls, const double* scale, const double* shift,
                      double* rows, double* ws, unsigned* tickets, int B, int C, int H, int W, int ncls, mau_stream_t stream);
 
+/* ---- scenario sessions: a painted canvas -> the network's input, the head's output -> temperature change (the app's per-click path,
+ *      app/Home.py:333-411 with app/processing_utils.py:70-181), ONE launch each.  Additive to ABI 5 ----
+ * mau_scenario_pack builds N scenario inputs from ONE base tile:
+ *   dw_t1 (H,W) uint8 class ids; rgb (3,H,W) fp32, raw 0..255; ndvi (H,W) fp32; temp (H,W) fp32, raw degrees C;
+ *   canvas (N,Hc,Wc,4) uint8 RGBA (4-byte aligned); yidx (H), xidx (W) int32: the canvas row / column a destination row / column
+ *   samples (nearest-neighbour resize as two tables; an entry outside the canvas is clamped); palette (ncls,3) uint8 RGB, class order;
+ *   norm: 8 fp64 = rgb_mean[3], rgb_std[3], temp_mean, temp_std.  ncls in [1, mau_scenario_max_classes()].
+ * Per pixel p = canvas[n, yidx[y], xidx[x]]: alpha > 0 -> the class of the lowest-index palette entry of smallest squared RGB
+ * distance (integers: equal to scipy's cdist + argmin, the first minimum on a tie), else dw_t1 (canvas_to_dw_map, :70-110).
+ *   dw_t2 (N,H,W) uint8 = that class map;
+ *   out (N,H,W,ldo) in `dtype`, ldo % 8 == 0, ldo >= 2 ncls + 5, the reference's channel order (:146-148):
+ *     [one-hot dw_t1 (ncls) | rgb (3) | ndvi | temp | one-hot dw_t2 (ncls) | zeros up to ldo]
+ *   rgb = ((double)v / 255.0 - mean) / std and temp = ((double)v - mean) / std in fp64 with IEEE division, rounded to float once
+ *   (the float64 numpy of :136-139 followed by .float(), bit for bit), ndvi as it is; then rounded to `dtype` as
+ *   mau_pack_tile_onehot does.  The base tile is read once per scenario. */
+int mau_scenario_max_classes(void);
+int mau_scenario_pack(const unsigned char* dw_t1, const float* rgb, const float* ndvi, const float* temp, const unsigned char* canvas,
+                      const int* yidx, const int* xidx, const unsigned char* palette, const double* norm, void* out, int ldo,
+                      unsigned char* dw_t2, int dtype, int N, int H, int W, int Hc, int Wc, int ncls, mau_stream_t stream);
+/* mau_scenario_result: out (N,2,H,W) fp32 NCHW, the head's output (channel 0 NDVI, channel 1 normalised temperature);
+ * temp_orig (H,W) fp32 raw degrees C, or NULL; dw_t1 (H,W), dw_t2 (N,H,W) uint8.
+ *   ndvi (N,H,W) fp32   = channel 0;
+ *   temp_c (N,H,W) fp32 = fl32(fl32(out * fl32(temp_std)) + fl32(temp_mean)): two separately rounded fp32 operations, never an
+ *                         FMA -- numpy on a float32 array with Python-float scalars (denormalize_output, :179-181);
+ *   delta (N,H,W) fp32  = fl32(temp_c - temp_orig) (app/Home.py:400);
+ *   rows (N, mau_scenario_result_row_elems() = 5) fp64:
+ *     [0] mean delta (:410)  [1] min delta  [2] max delta (NaNs skipped by both)  [3] pixels with dw_t2 != dw_t1
+ *     [4] mean delta over those pixels, NaN when there are none.
+ * temp_orig == NULL: delta (may be NULL) is not written and rows[0], [1], [2], [4] are NaN.
+ * Sums are fp64 in a fixed order: a workgroup owns a run of pixels of ONE scenario (mau_scenario_result_chunks(H, W) workgroups
+ * per scenario, a function of H * W alone), the workgroup that draws the scenario's last ticket adds its partials in chunk order --
+ * no float atomics; a row's bits do not depend on N or on the scenario's place in the batch, and repeat.
+ * ws: fp64 workspace of mau_scenario_result_ws_elems(N, H, W) elements; tickets: a ZEROED mau_reduce_tickets_elems() buffer (left
+ * zeroed; see mau_reduce_rows_f64).  One launch per mau_reduce_tickets_elems() scenarios. */
+int mau_scenario_result_row_elems(void);
+int mau_scenario_result_chunks(int H, int W);
+size_t mau_scenario_result_ws_elems(int N, int H, int W);
+int mau_scenario_result(const float* out, const float* temp_orig, const unsigned char* dw_t1, const unsigned char* dw_t2, double temp_mean,
+                        double temp_std, float* ndvi, float* temp_c, float* delta, double* rows, double* ws, unsigned* tickets, int N,
+                        int H, int W, mau_stream_t stream);
+
 /* ---- loss: F.mse_loss (src/utils/losses.py:27-39) -------------------------- */
 /* loss[0] = mean((out-tgt)^2) (fp64 accumulation, fixed order); dout (optional) = 2*(out-tgt)/n;
  * partial: fp64 workspace of mau_mse_blocks(n) elements. */

@@ -16,15 +16,18 @@ from . import data                      # noqa: F401  (input pipeline: compact t
 
 
 def __getattr__(name):
-    # ``mau_amd.sensitivity`` (metadata sensitivity sweeps) and ``mau_amd.evaluate`` (test-split evaluation) are also command
-    # lines, ``python -m mau_amd.sensitivity`` / ``python -m mau_amd.evaluate``: they are imported on first use, so that running
-    # one as a script does not find it in sys.modules already
-    if name in ("sensitivity", "evaluate"):
-        import importlib
+    # ``mau_amd.sensitivity`` (metadata sensitivity sweeps), ``mau_amd.evaluate`` (test-split evaluation) and ``mau_amd.scenario``
+    # (scenario sessions of the app) are also command lines, ``python -m mau_amd.sensitivity`` / ``.evaluate`` / ``.scenario``: they
+    # are imported on first use, so that running one as a script does not find it in sys.modules already
+    import importlib
+    if name in ("sensitivity", "evaluate", "scenario"):
         return importlib.import_module("." + name, __name__)
+    if name in ("ScenarioSession", "ScenarioResult"):
+        return getattr(importlib.import_module(".scenario", __name__), name)
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")
 
 
 __all__ = ["UrbanPredictor", "UrbanPredictor_unet", "UrbanPredictor_unetpp", "VGGBlock", "MetadataEncoder",
            "TemporalEncoder", "compute_loss_mse", "compute_loss_mse_gradient", "compute_loss_l1_grad_ssim", "gradient_loss",
-           "GraphedInference", "GraphedTrainStep", "AdamW", "Adam", "SGD", "mark_params_updated", "sensitivity", "evaluate"]
+           "GraphedInference", "GraphedTrainStep", "AdamW", "Adam", "SGD", "mark_params_updated", "sensitivity", "evaluate", "scenario",
+           "ScenarioSession", "ScenarioResult"]

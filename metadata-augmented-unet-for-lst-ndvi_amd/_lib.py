@@ -117,6 +117,12 @@ PROTOTYPES = {
     "mau_eval_metrics_chunks": (_i, [_i, _i]),
     "mau_eval_metrics_ws_elems": (_sz, [_i, _i, _i, _i, _i]),
     "mau_eval_metrics": (_i, [_p, _p, _p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _p]),
+    "mau_scenario_max_classes": (_i, []),
+    "mau_scenario_pack": (_i, [_p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _i, _p, _i, _i, _i, _i, _i, _i, _i, _p]),
+    "mau_scenario_result_row_elems": (_i, []),
+    "mau_scenario_result_chunks": (_i, [_i, _i]),
+    "mau_scenario_result_ws_elems": (_sz, [_i, _i, _i]),
+    "mau_scenario_result": (_i, [_p, _p, _p, _p, _d, _d, _p, _p, _p, _p, _p, _p, _i, _i, _i, _p]),
     "mau_mse_blocks": (_i, [_i64]),
     "mau_l1_gradient_blocks": (_i, [_i64]),
     "mau_l1_gradient_loss": (_i, [_p, _p, _p, _p, _p, _f, _f, _i, _i, _i, _i, _p]),

@@ -1,0 +1,416 @@
+"""Scenario sessions: a painted canvas -> forecast and temperature change, on the device (the reference's Streamlit app).
+
+In the app a user paints land-cover changes on a canvas and asks for the forecast (app/Home.py:333-411).  Per click the
+reference resizes the RGBA canvas, matches every pixel against the palette (``cdist`` + ``argmin``), merges with the
+original class map by alpha, normalises five planes in float64, builds two one-hot stacks, copies a dense 23-plane fp32
+tensor to the device (92 B per pixel), and after the forward copies the output back, un-normalises it, subtracts the
+original temperature raster and takes the mean (app/processing_utils.py:70-181).  Here
+
+* ``mau_scenario_pack`` is ONE launch from the canvas (4 B per canvas pixel) and the resident base tile to the network's
+  input and the edited class map -- nearest-neighbour resize through two index tables, integer palette match, fp64
+  normalisation, one-hot channels, NHWC-ld layout and the 16-bit cast;
+* ``mau_scenario_result`` is ONE launch from the head's output to NDVI, temperature in degrees C, its difference to the
+  original raster and five fp64 statistics per scenario (fixed summation order, no float atomics);
+* ``ScenarioSession`` captures pack -> network -> result into one hipGraph: an edit costs one canvas upload, one replay
+  and one small read-back.  ``scenarios=N`` evaluates N canvases of one base tile per replay.
+
+The host helpers (pure numpy) spell the reference's own path; ``prepare_input_host`` is the truth the device path is
+tested against, bit for bit.
+
+    python -m mau_amd.scenario CHECKPOINT --tile tile.npz --palette-json P --metrics-json M [--precision fp16] [--output out.npz]
+"""
+from __future__ import annotations
+
+import json
+from typing import Optional, Sequence, Tuple
+
+import numpy as np
+import torch
+
+from . import functional as F_
+from .functional import Act, call, dtype_code, lib, pad8
+
+N_CONT = 5               # rgb (3) + ndvi + temperature
+METRIC_KEYS = ("rgb_mean", "rgb_std", "temp_mean", "temp_std", "meta_mean", "meta_std", "temp_series_mean", "temp_series_std")
+STAT_NAMES = ("mean_delta", "min_delta", "max_delta", "edited_pixels", "mean_delta_edited")
+
+
+# --------------------------------------------------------------------------- #
+# host helpers (numpy): the reference's path, in its own arithmetic
+# --------------------------------------------------------------------------- #
+def nearest_index_table(n_in: int, n_out: int) -> np.ndarray:
+    """Source index per destination index of Pillow's nearest-neighbour resize from ``n_in`` to ``n_out`` samples (int32).
+    Pillow's affine scaler starts at half a step and ACCUMULATES the step in double; the closed form
+    ``floor((x + 0.5) * n_in / n_out)`` rounds differently (200 -> 250 disagrees on many pixels)."""
+    if n_in < 1 or n_out < 1:
+        raise ValueError(f"nearest_index_table: sizes must be positive, got {n_in} -> {n_out}")
+    a = float(n_in) / float(n_out)
+    xo = 0.5 * a
+    idx = np.empty(n_out, dtype=np.int32)
+    for x in range(n_out):
+        idx[x] = min(int(xo), n_in - 1)
+        xo += a
+    return idx
+
+
+def palette_from_hex(colours: Sequence[str]) -> np.ndarray:
+    """``['#419bdf', ...]`` in class order -> (ncls, 3) uint8 (the reference's ``hex_to_rgb``, :49-51)."""
+    return np.array([[int(c.lstrip("#")[i:i + 2], 16) for i in (0, 2, 4)] for c in colours], dtype=np.uint8)
+
+
+def _palette(palette) -> np.ndarray:
+    p = np.asarray(palette)
+    if p.ndim != 2 or p.shape[1] != 3 or p.dtype != np.uint8 or p.shape[0] < 1:
+        raise ValueError("palette must be an (ncls, 3) uint8 array, ncls >= 1")
+    return np.ascontiguousarray(p)
+
+
+def canvas_to_dw_map_host(canvas: np.ndarray, target_shape: Tuple[int, int], palette, original_map: Optional[np.ndarray] = None) -> np.ndarray:
+    """``canvas_to_dw_map`` (:70-110): (Hc, Wc, 4) RGBA -> (H, W) uint8 class map.  The canvas is resized with nearest
+    neighbour; a pixel takes the palette entry of smallest RGB distance (the first on a tie -- integer squared distances,
+    which order exactly as ``cdist``'s); with ``original_map``, pixels of alpha 0 keep its class."""
+    canvas, palette = np.asarray(canvas), _palette(palette)
+    if canvas.ndim != 3 or canvas.shape[2] != 4:
+        raise ValueError(f"canvas must be (Hc, Wc, 4) RGBA, got {canvas.shape}")
+    H, W = int(target_shape[0]), int(target_shape[1])
+    arr = canvas.astype(np.uint8)[nearest_index_table(canvas.shape[0], H)][:, nearest_index_table(canvas.shape[1], W)]
+    diff = arr[:, :, None, :3].astype(np.int32) - palette[None, None].astype(np.int32)
+    nearest = np.argmin((diff * diff).sum(axis=3), axis=2)
+    if original_map is None:
+        return nearest.astype(np.uint8)
+    original_map = np.asarray(original_map)
+    if original_map.ndim == 3:
+        original_map = original_map[0]
+    return np.where(arr[:, :, 3] > 0, nearest, original_map).astype(np.uint8)
+
+
+def _check_metrics(metrics: dict, keys=METRIC_KEYS[:4]):
+    missing = [k for k in keys if k not in metrics]
+    if missing:
+        raise ValueError(f"metrics lacks {missing} (the keys of normalization_metrics.json)")
+
+
+def _norm_row(metrics: dict) -> np.ndarray:
+    _check_metrics(metrics)
+    row = np.array(list(metrics["rgb_mean"]) + list(metrics["rgb_std"]) + [metrics["temp_mean"], metrics["temp_std"]], dtype=np.float64)
+    if row.shape != (8,):
+        raise ValueError("metrics: rgb_mean and rgb_std hold three values each")
+    return row
+
+
+def normalized_planes_host(rgb, ndvi, temp, metrics: dict) -> np.ndarray:
+    """The five continuous planes of the network's input, (5, H, W) fp32: float64 arithmetic rounded to float once (:136-139, :149)."""
+    _check_metrics(metrics)
+    row = _norm_row(metrics)
+    colour = np.asarray(rgb, dtype=np.float64)
+    h, w = colour.shape[-2:]
+    planes = np.empty((N_CONT, h, w), dtype=np.float64)
+    planes[:3] = (colour.reshape(3, h, w) / 255.0 - row[0:3].reshape(3, 1, 1)) / row[3:6].reshape(3, 1, 1)
+    planes[3] = np.asarray(ndvi, dtype=np.float64).reshape(h, w)
+    planes[4] = (np.asarray(temp, dtype=np.float64).reshape(h, w) - row[6]) / row[7]
+    return planes.astype(np.float32)
+
+
+def prepare_input_host(dw_t1, rgb, ndvi, temp, canvas, palette, metrics: dict) -> np.ndarray:
+    """The dense input of ``prepare_input`` (:134-149) as a (1, 2 ncls + 5, H, W) fp32 array:
+    ``[one-hot dw_t1 | rgb | ndvi | temp | one-hot dw_t2]``, the planes normalised in float64 and rounded to float once."""
+    palette = _palette(palette)
+    dw_t1 = np.asarray(dw_t1)
+    if dw_t1.ndim == 3:
+        dw_t1 = dw_t1[0]
+    dw_t2 = canvas_to_dw_map_host(canvas, dw_t1.shape, palette, original_map=dw_t1)
+    ids = np.arange(palette.shape[0], dtype=np.int64).reshape(-1, 1, 1)
+    dense = np.concatenate([(dw_t1[None].astype(np.int64) == ids).astype(np.float32), normalized_planes_host(rgb, ndvi, temp, metrics),
+                            (dw_t2[None].astype(np.int64) == ids).astype(np.float32)])
+    return dense[None]
+
+
+def metadata_row(lat, lon, population, year_t1, month_t1, year_t2, month_t2, meta_mean, meta_std) -> np.ndarray:
+    """The (1, 8) fp32 metadata row of :151-160: z-scored (lat, lon, population, years between the dates), then the two dates."""
+    mean, std = np.asarray(meta_mean, dtype=np.float64), np.asarray(meta_std, dtype=np.float64)
+    if mean.shape != (4,) or std.shape != (4,):
+        raise ValueError("metadata_row: meta_mean and meta_std hold four values each")
+    row = np.empty((1, 8), dtype=np.float64)
+    row[0, :4] = (np.array([lat, lon, population, (year_t2 - year_t1) + (month_t2 - month_t1) / 12.0], dtype=np.float64) - mean) / std
+    row[0, 4:] = year_t1, month_t1, year_t2, month_t2
+    return row.astype(np.float32)
+
+
+def normalize_temp_series(ts, metrics: dict) -> np.ndarray:
+    """The (1, T) fp32 temperature series of :167-168."""
+    _check_metrics(metrics, ("temp_series_mean", "temp_series_std"))
+    series = np.asarray(ts, dtype=np.float64).reshape(1, -1)
+    return ((series - float(metrics["temp_series_mean"])) / float(metrics["temp_series_std"])).astype(np.float32)
+
+
+# --------------------------------------------------------------------------- #
+# the two launches
+# --------------------------------------------------------------------------- #
+def _dev(t, what: str, dtype, shape=None) -> torch.Tensor:
+    if not isinstance(t, torch.Tensor):
+        raise TypeError(f"{what} must be a torch tensor on the device, got {type(t).__name__}")
+    F_._require_cuda(t, what)
+    if t.dtype != dtype:
+        raise TypeError(f"{what} must be {dtype}, got {t.dtype}")
+    if shape is not None and tuple(t.shape) != tuple(shape):
+        raise ValueError(f"{what} must be {tuple(shape)}, got {tuple(t.shape)}")
+    return t.contiguous()
+
+
+def _const(v, dtype, dev) -> torch.Tensor:
+    """A small host array (or device tensor) as a contiguous device tensor."""
+    if isinstance(v, torch.Tensor):
+        return v.to(device=dev, dtype=dtype).contiguous()
+    return torch.from_numpy(np.ascontiguousarray(v)).to(dtype).to(dev)
+
+
+def _tile(dw_t1, rgb, ndvi, temp):
+    """The base tile, checked: dw_t1 (H,W) uint8, rgb (3,H,W), ndvi (H,W) | (1,H,W), temp likewise, fp32, on the device."""
+    dw_t1 = _dev(dw_t1, "dw_t1", torch.uint8)
+    if dw_t1.dim() == 3 and dw_t1.shape[0] == 1:
+        dw_t1 = dw_t1[0]
+    if dw_t1.dim() != 2:
+        raise ValueError(f"dw_t1 must be (H, W), got {tuple(dw_t1.shape)}")
+    H, W = dw_t1.shape
+    rgb = _dev(rgb, "rgb", torch.float32, (3, H, W))
+    ndvi = _dev(ndvi.reshape(H, W) if isinstance(ndvi, torch.Tensor) and ndvi.numel() == H * W else ndvi, "ndvi", torch.float32, (H, W))
+    temp = _dev(temp.reshape(H, W) if isinstance(temp, torch.Tensor) and temp.numel() == H * W else temp, "temp", torch.float32, (H, W))
+    return dw_t1, rgb, ndvi, temp
+
+
+def _canvas4(canvas: torch.Tensor) -> torch.Tensor:
+    if canvas.dim() == 3:
+        canvas = canvas[None]
+    if canvas.dim() != 4 or canvas.shape[3] != 4:
+        raise ValueError(f"canvas must be (Hc, Wc, 4) or (N, Hc, Wc, 4) RGBA, got {tuple(canvas.shape)}")
+    return canvas
+
+
+class _Tables:
+    """The device-side constants of ``mau_scenario_pack`` for one (tile shape, canvas shape, palette, metrics)."""
+
+    def __init__(self, tile_shape, canvas_shape, palette, metrics: dict, dev):
+        palette = _palette(palette)
+        self.ncls = palette.shape[0]
+        if self.ncls > lib.mau_scenario_max_classes():
+            raise ValueError(f"mau_scenario_pack takes at most {lib.mau_scenario_max_classes()} classes, the palette has {self.ncls}")
+        self.palette = _const(palette, torch.uint8, dev)
+        self.norm = _const(_norm_row(metrics), torch.float64, dev)
+        self.yidx = _const(nearest_index_table(canvas_shape[0], tile_shape[0]), torch.int32, dev)
+        self.xidx = _const(nearest_index_table(canvas_shape[1], tile_shape[1]), torch.int32, dev)
+
+
+def _pack(dw_t1, rgb, ndvi, temp, canvas, tb: _Tables, dtype: torch.dtype):
+    N, Hc, Wc, _ = canvas.shape
+    H, W = dw_t1.shape
+    C = 2 * tb.ncls + N_CONT
+    out = torch.empty((N, H, W, pad8(C)), dtype=dtype, device=dw_t1.device)
+    dw_t2 = torch.empty((N, H, W), dtype=torch.uint8, device=dw_t1.device)
+    call("mau_scenario_pack", dw_t1.data_ptr(), rgb.data_ptr(), ndvi.data_ptr(), temp.data_ptr(), canvas.data_ptr(), tb.yidx.data_ptr(),
+         tb.xidx.data_ptr(), tb.palette.data_ptr(), tb.norm.data_ptr(), out.data_ptr(), out.shape[-1], dw_t2.data_ptr(), dtype_code(dtype),
+         N, H, W, Hc, Wc, tb.ncls, F_._stream())
+    return Act(out, C), dw_t2
+
+
+def pack(dw_t1, rgb, ndvi, temp, canvas, palette, metrics: dict, dtype: torch.dtype = torch.bfloat16) -> Tuple[Act, torch.Tensor]:
+    """One launch (``mau_scenario_pack``): base tile + N painted canvases -> (the network's input ``Act`` (N, H, W, ld),
+    dw_t2 (N, H, W) uint8).  dw_t1 (H,W) uint8, rgb (3,H,W) raw 0..255, ndvi (H,W), temp (H,W) raw degrees C, fp32; canvas
+    (Hc,Wc,4) or (N,Hc,Wc,4) uint8 RGBA; all on the device.  palette (ncls,3) uint8 and the metrics dict are host values.
+    Bit-identical to ``data.pack_tiles`` on the class maps and normalised planes of ``prepare_input_host``."""
+    dw_t1, rgb, ndvi, temp = _tile(dw_t1, rgb, ndvi, temp)
+    canvas = _canvas4(_dev(canvas, "canvas", torch.uint8))
+    tb = _Tables(dw_t1.shape, canvas.shape[1:3], palette, metrics, dw_t1.device)
+    return _pack(dw_t1, rgb, ndvi, temp, canvas, tb, dtype)
+
+
+class ScenarioResult:
+    """What ``mau_scenario_result`` wrote: ``ndvi``, ``temp_c``, ``delta`` (N, H, W) fp32 (``delta`` None without an original
+    raster), ``dw_t2`` (N, H, W) uint8 and ``stats`` (N, 5) fp64, all on the device; the named statistics are views of ``stats``."""
+
+    def __init__(self, ndvi, temp_c, delta, dw_t2, stats):
+        self.ndvi, self.temp_c, self.delta, self.dw_t2, self.stats = ndvi, temp_c, delta, dw_t2, stats
+
+    mean_delta = property(lambda self: self.stats[:, 0])
+    min_delta = property(lambda self: self.stats[:, 1])
+    max_delta = property(lambda self: self.stats[:, 2])
+    edited_pixels = property(lambda self: self.stats[:, 3])
+    mean_delta_edited = property(lambda self: self.stats[:, 4])
+
+    def clone(self) -> "ScenarioResult":
+        return ScenarioResult(*(None if t is None else t.clone() for t in (self.ndvi, self.temp_c, self.delta, self.dw_t2, self.stats)))
+
+
+def result(output: torch.Tensor, temp_orig: Optional[torch.Tensor], dw_t1: torch.Tensor, dw_t2: torch.Tensor, temp_mean: float,
+           temp_std: float, tickets: Optional[torch.Tensor] = None) -> ScenarioResult:
+    """One launch (``mau_scenario_result``): the head's output (N, 2, H, W) fp32 -> :class:`ScenarioResult`.  temp_orig
+    (H, W) fp32 raw degrees C or None (no difference: the delta statistics are NaN); dw_t1 (H, W), dw_t2 (N, H, W) uint8.
+    ``temp_c = out * temp_std + temp_mean`` as float32 numpy computes it (two roundings); the statistics are fp64 sums in a
+    fixed order: a scenario's row does not depend on N, repeated calls agree bit for bit."""
+    output = _dev(output, "output", torch.float32)
+    if output.dim() != 4 or output.shape[1] != 2:
+        raise ValueError(f"output must be (N, 2, H, W), got {tuple(output.shape)}")
+    N, _, H, W = output.shape
+    dw_t1 = _dev(dw_t1, "dw_t1", torch.uint8, (H, W))
+    dw_t2 = _dev(dw_t2, "dw_t2", torch.uint8, (N, H, W))
+    if temp_orig is not None:
+        temp_orig = _dev(temp_orig, "temp_orig", torch.float32, (H, W))
+    dev = output.device
+    ndvi = torch.empty((N, H, W), dtype=torch.float32, device=dev)
+    temp_c = torch.empty_like(ndvi)
+    delta = torch.empty_like(ndvi) if temp_orig is not None else None
+    stats = torch.empty((N, lib.mau_scenario_result_row_elems()), dtype=torch.float64, device=dev)
+    ws = torch.empty(lib.mau_scenario_result_ws_elems(N, H, W), dtype=torch.float64, device=dev)
+    tickets = F_._tickets(dev) if tickets is None else tickets
+    call("mau_scenario_result", output.data_ptr(), None if temp_orig is None else temp_orig.data_ptr(), dw_t1.data_ptr(), dw_t2.data_ptr(),
+         float(temp_mean), float(temp_std), ndvi.data_ptr(), temp_c.data_ptr(), None if delta is None else delta.data_ptr(),
+         stats.data_ptr(), ws.data_ptr(), tickets.data_ptr(), N, H, W, F_._stream())
+    return ScenarioResult(ndvi, temp_c, delta, dw_t2, stats)
+
+
+# --------------------------------------------------------------------------- #
+# the session
+# --------------------------------------------------------------------------- #
+class ScenarioSession:
+    """``ScenarioSession(model, dw_t1, rgb, ndvi, temp, metadata, temp_series, palette=..., metrics=...)(canvas) -> ScenarioResult``.
+
+    The base tile (device tensors: dw_t1 (H,W) uint8; rgb (3,H,W), ndvi (H,W), temp (H,W) fp32, raw values), the metadata row
+    (1,F) and the temperature series (1,T) are fixed at construction; ``palette`` is the (ncls,3) uint8 colour table in class
+    order and ``metrics`` a dict with the keys of ``normalization_metrics.json``.  The session freezes the model
+    (``freeze_inference``), warms up on a side stream and captures ONE hipGraph: ``mau_scenario_pack`` -> the network ->
+    ``mau_scenario_result``.  A call copies the canvas -- (Hc,Wc,4) or (N,Hc,Wc,4) uint8, host array or device tensor, of the
+    ``canvas_shape`` and ``scenarios`` given here -- into the session's buffer and replays.  ``temp_orig``: the raster the
+    temperature change is taken against (app/Home.py:376-400); None = ``temp``.  ``clone_output=False`` returns the session's
+    own buffers, valid until the next call.  Reload weights -> build a new session."""
+
+    def __init__(self, model: torch.nn.Module, dw_t1, rgb, ndvi, temp, metadata, temp_series, *, palette, metrics: dict,
+                 canvas_shape: Tuple[int, int] = (512, 512), scenarios: int = 1, temp_orig=None, warmup: int = 2,
+                 clone_output: bool = True):
+        dw_t1, rgb, ndvi, temp = _tile(dw_t1, rgb, ndvi, temp)
+        for t, what in ((metadata, "metadata"), (temp_series, "temp_series")):
+            F_._require_cuda(t, f"ScenarioSession({what})")
+        if scenarios < 1:
+            raise ValueError("scenarios must be >= 1")
+        _check_metrics(metrics)
+        dev = dw_t1.device
+        N, (Hc, Wc) = int(scenarios), (int(canvas_shape[0]), int(canvas_shape[1]))
+        self.model = model.eval()
+        self.clone_output = clone_output
+        if hasattr(self.model, "freeze_inference"):
+            self.model.freeze_inference(True)
+        net = getattr(self.model, "model", self.model)
+        self.dtype = net._rt.dtype
+        self._tile = tuple(t.detach().clone() for t in (dw_t1, rgb, ndvi, temp))
+        self._temp_orig = self._tile[3] if temp_orig is None else _dev(temp_orig, "temp_orig", torch.float32, tuple(dw_t1.shape)).detach().clone()
+        self._tables = _Tables(dw_t1.shape, (Hc, Wc), palette, metrics, dev)
+        self._mean, self._std = float(metrics["temp_mean"]), float(metrics["temp_std"])
+        self._md = metadata.detach().float().reshape(1, -1).expand(N, -1).contiguous()
+        self._ts = temp_series.detach().float().reshape(1, -1).expand(N, -1).contiguous()
+        self._canvas = torch.zeros((N, Hc, Wc, 4), dtype=torch.uint8, device=dev)
+        self._stage = torch.empty((N, Hc, Wc, 4), dtype=torch.uint8).pin_memory()       # host canvases travel through pinned memory
+        self._staged = torch.cuda.Event()
+        # the tickets of the captured reduction are the session's own: a replay never shares them with a launch on another stream
+        self._tickets = torch.zeros(lib.mau_reduce_tickets_elems(), dtype=torch.int32, device=dev)
+        side = torch.cuda.Stream(device=dev)
+        side.wait_stream(torch.cuda.current_stream())
+        with torch.cuda.stream(side), torch.no_grad():
+            for _ in range(max(1, warmup)):            # packs weights, sets kernel attributes, warms the allocator
+                self._run()
+        torch.cuda.current_stream().wait_stream(side)
+        self.graph = torch.cuda.CUDAGraph()
+        with torch.no_grad(), torch.cuda.graph(self.graph):
+            self._out = self._run()
+
+    def _run(self) -> ScenarioResult:
+        x, dw_t2 = _pack(*self._tile, self._canvas, self._tables, self.dtype)
+        return result(self.model(x, self._ts, self._md), self._temp_orig, self._tile[0], dw_t2, self._mean, self._std, self._tickets)
+
+    @property
+    def canvas(self) -> torch.Tensor:
+        """The session's own (N, Hc, Wc, 4) uint8 canvas buffer: a caller that fills it and passes it to ``__call__`` pays no copy."""
+        return self._canvas
+
+    @torch.no_grad()
+    def __call__(self, canvas) -> ScenarioResult:
+        if isinstance(canvas, torch.Tensor):
+            src = canvas if canvas.dim() != 3 else canvas[None]
+        else:
+            src = np.asarray(canvas)
+            src = src if src.ndim != 3 else src[None]
+        if tuple(src.shape) != tuple(self._canvas.shape):
+            raise ValueError(f"ScenarioSession was captured for canvases of shape {tuple(self._canvas.shape)} (or one of "
+                             f"{tuple(self._canvas.shape[1:])} when scenarios == 1), got {tuple(np.shape(canvas))}")
+        if str(src.dtype) not in ("uint8", "torch.uint8"):
+            raise TypeError(f"canvas must be uint8 RGBA, got {src.dtype}")
+        if isinstance(src, torch.Tensor) and src.is_cuda:
+            if src.data_ptr() != self._canvas.data_ptr():
+                self._canvas.copy_(src, non_blocking=True)
+        else:
+            self._staged.synchronize()                  # the previous call's copy out of the pinned buffer has finished
+            self._stage.copy_(src if isinstance(src, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(src)))
+            self._canvas.copy_(self._stage, non_blocking=True)
+            self._staged.record()
+        self.graph.replay()
+        return self._out.clone() if self.clone_output else self._out
+
+
+# --------------------------------------------------------------------------- #
+# CLI
+# --------------------------------------------------------------------------- #
+def run_tile(checkpoint: str, tile: str, palette_json: str, metrics_json: str, precision: str = "fp16", output: str = "",
+             device: str = "cuda") -> dict:
+    """Body of the CLI: one session call on the tile of ``tile`` (.npz: dw, rgb, ndvi, temp, canvas, metadata_raw = (lat, lon,
+    population, year_t1, month_t1, year_t2, month_t2), optionally temp_series (raw) and temp_orig).  Returns -- and with
+    ``output`` writes as .npz -- ndvi, temp_c, delta, dw_t2, stats and the statistics by name."""
+    from .checkpoint import load_model
+    with open(palette_json) as f:
+        palette = palette_from_hex(json.load(f))
+    with open(metrics_json) as f:
+        metrics = json.load(f)
+    _check_metrics(metrics, METRIC_KEYS)
+    d = np.load(tile)
+    md = metadata_row(*[float(v) for v in d["metadata_raw"]], metrics["meta_mean"], metrics["meta_std"])
+    ts = normalize_temp_series(d["temp_series"], metrics) if "temp_series" in d else np.zeros((1, 60), dtype=np.float32)     # (:172-175)
+    dw = np.asarray(d["dw"])
+    dw = dw[0] if dw.ndim == 3 else dw
+    H, W = dw.shape
+    canvas = np.ascontiguousarray(d["canvas"], dtype=np.uint8)
+    model = load_model(checkpoint, device=device, spatial_channels=2 * palette.shape[0] + N_CONT, seq_len=ts.shape[1])
+    model.set_precision(precision)
+    dev = lambda a, dt: torch.from_numpy(np.ascontiguousarray(a, dtype=dt)).to(device)       # noqa: E731
+    sess = ScenarioSession(model, dev(dw, np.uint8), dev(np.reshape(d["rgb"], (3, H, W)), np.float32), dev(np.reshape(d["ndvi"], (H, W)), np.float32),
+                           dev(np.reshape(d["temp"], (H, W)), np.float32), dev(md, np.float32), dev(ts, np.float32), palette=palette,
+                           metrics=metrics, canvas_shape=canvas.shape[-3:-1], scenarios=1 if canvas.ndim == 3 else canvas.shape[0],
+                           temp_orig=dev(np.reshape(d["temp_orig"], (H, W)), np.float32) if "temp_orig" in d else None)
+    r = sess(canvas)
+    stats = r.stats.cpu().numpy()
+    res = {"ndvi": r.ndvi.cpu().numpy(), "temp_c": r.temp_c.cpu().numpy(), "delta": r.delta.cpu().numpy(), "dw_t2": r.dw_t2.cpu().numpy(),
+           "stats": stats, **{name: stats[:, i] for i, name in enumerate(STAT_NAMES)}}
+    if output:
+        np.savez(output, **res)
+    return res
+
+
+def _cli():
+    import typer
+    app = typer.Typer(add_completion=False)
+
+    @app.command()
+    def main(checkpoint: str = typer.Argument(..., help="reference-layout .pth (src/train.py:303-316)"),
+             tile: str = typer.Option(..., help=".npz: dw, rgb, ndvi, temp, canvas, metadata_raw [, temp_series, temp_orig]"),
+             palette_json: str = typer.Option(..., help="the palette's hex colours in class order"),
+             metrics_json: str = typer.Option(..., help="normalization_metrics.json"),
+             precision: str = "fp16", output: str = "", device: str = "gpu"):
+        """One scenario (canvas edit -> forecast and temperature change) of a checkpoint on one tile."""
+        if device.lower() == "cpu":
+            raise typer.BadParameter("this is the MI355X-native path: --device gpu (there is no CPU fallback)")
+        res = run_tile(checkpoint, tile, palette_json, metrics_json, precision, output, "cuda:0" if device.lower() == "gpu" else device)
+        for n in range(res["stats"].shape[0]):
+            typer.echo("scenario %d: " % n + ", ".join(f"{name} {res[name][n]:.6g}" for name in STAT_NAMES))
+        if output:
+            typer.echo(f"Saved scenario result to {output}")
+
+    return app
+
+
+if __name__ == "__main__":
+    _cli()()
