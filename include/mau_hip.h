@@ -522,6 +522,26 @@ size_t mau_ssim_ws_elems(int B, int C, int H, int W);
 int mau_ssim_loss(const float* out, const float* tgt, double* ws, float* per_image, float* loss, int prep, int B, int C,
                   int H, int W, mau_stream_t stream);
 
+/* ---- every term of compute_all_loss (src/utils/losses.py:101-115) for one batch in ONE launch: what the validation pass
+ *      (src/train.py:20-60) averages.  Value only.  Additive to ABI 5 ----
+ * out/tgt (B,2,H,W) fp32 (C != 2 is refused: the channel preparation of :72-84 is defined for NDVI and temperature only).
+ * terms (8 fp32):
+ *   [0] mse (:33)   [1] pixel = mean|out-tgt| (:67)   [2] mean| |dy out|-|dy tgt| | (:22)   [3] the same in x (:23)
+ *   [4] gradient = [2] + [3] (:25)   [5] ssim = 1 - mean(ssim_per_image) (:89), geometry, window and channel preparation of
+ *   mau_ssim_loss with prep != 0   [6] [0] + lambda_grad * [4] (:51)   [7] [1] + lambda_grad * [4] + lambda_ssim * [5] (:92);
+ *   [4], [6] and [7] are fp32 operations in the reference's order, never contracted.
+ * ssim_per_image (B fp32): SSIM per sample, as mau_ssim_loss gives it.
+ * acc (8 fp64, or NULL): acc[k] += B * (double)terms[k] -- the reference's `v.item() * len(batch)` (src/train.py:42,48) kept on the
+ *   device; a pass over a split reads it back once.  The caller zeroes it before the first batch.
+ * Sums are fp64 in a fixed order: a workgroup owns one 16x16 tile of the SSIM map of one (image, channel) plane and a disjoint
+ * rectangle of its full-resolution pixels, the workgroup that draws the last ticket adds the partials in index order -- no float
+ * atomics; the results repeat bit for bit.  An image smaller than the 11x11 window after pooling is refused.
+ * ws: fp64 workspace of mau_loss_terms_ws_elems(B, C, H, W) elements; tickets: a ZEROED buffer of at least one uint32
+ * (mau_reduce_tickets_elems() entries will do), left zeroed; see mau_reduce_rows_f64. */
+size_t mau_loss_terms_ws_elems(int B, int C, int H, int W);
+int mau_loss_terms(const float* out, const float* tgt, double* ws, unsigned* tickets, float* terms, float* ssim_per_image,
+                   double* acc, float lambda_grad, float lambda_ssim, int B, int C, int H, int W, mau_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -4,6 +4,7 @@
 * ``gradient_loss``               :5-25    mean | |dy pred| - |dy tgt| | + same in x    -> HIP kernel
 * ``compute_loss_mse_gradient``   :41-57   mse + 0.1 * gradient
 * ``compute_loss_l1_grad_ssim``   :59-99   l1 + 0.1 * gradient + 0.5 * (1 - ssim)       (the yaml default, conf/config.yaml:42)
+* ``compute_all_loss``            :101-115 every term above, value only                 -> ONE HIP launch (``mau_loss_terms``)
 
 In the reference the SSIM values pass through ``torch.Tensor(ssim_vals)`` (:89-96), which detaches them: the SSIM
 term changes the reported number, never the gradient.  ``piq`` (the SSIM provider) is not available in the
@@ -15,7 +16,7 @@ gradient is pinned by fixture ``g9_losses.npz``.
 """
 import torch
 
-from .functional import L1GradientLoss, MSELoss, _require_cuda, _stream
+from .functional import L1GradientLoss, MSELoss, _require_cuda, _stream, _tickets
 from ._lib import call, lib
 
 
@@ -59,3 +60,40 @@ def compute_loss_l1_grad_ssim(outputs, targets, lambda_grad=0.1, lambda_ssim=0.5
     s, _ = ssim_loss(outputs, targets)                                                                     # :72-97
     total = l1 + lambda_grad * g + lambda_ssim * s
     return {"total": total, "pixel": l1, "gradient": g, "ssim": s}
+
+
+# index of every key of the reference's compute_all_loss dict in the ``terms`` of mau_loss_terms (include/mau_hip.h); 'total' is the
+# l1-gradient-ssim total, because that dict is merged last (src/utils/losses.py:112-113)
+ALL_LOSS_TERMS = {"total": 7, "mse": 0, "gradient": 4, "pixel": 1, "ssim": 5}
+TERM_MSE_GRADIENT_TOTAL = 6
+
+
+def loss_terms(outputs, targets, lambda_grad=0.1, lambda_ssim=0.5, acc=None):
+    """Every loss term of the batch in ONE launch (``mau_loss_terms``, csrc/loss_terms.hip).  Returns (terms (8,) fp32, per-image
+    SSIM (B,)); value only.  ``acc``: an 8-element float64 device tensor that additionally receives ``B * terms`` -- the sums of a
+    validation pass stay on the device.  A batch the kernel has no SSIM for (not two channels, or smaller than the 11x11 window
+    after pooling) raises ``ValueError`` before anything is launched."""
+    _require_cuda(outputs, "compute_all_loss")
+    o = outputs.detach().contiguous().float()
+    t = targets.detach().contiguous().float()
+    if o.dim() != 4 or o.shape != t.shape:
+        raise ValueError(f"compute_all_loss: outputs {tuple(o.shape)} and targets {tuple(t.shape)} must be equal (B,C,H,W) shapes")
+    B, C, H, W = o.shape
+    n_ws = lib.mau_loss_terms_ws_elems(B, C, H, W)
+    if C != 2 or n_ws == 0:
+        raise ValueError(f"compute_all_loss: needs (B,2,H,W) maps of at least 11x11 pixels after SSIM pooling, got {tuple(o.shape)}")
+    if acc is not None and (acc.dtype != torch.float64 or acc.numel() < 8 or acc.device != o.device or not acc.is_contiguous()):
+        raise ValueError("compute_all_loss: acc must be a contiguous float64 tensor of 8 elements on the outputs' device")
+    ws = torch.empty(n_ws, dtype=torch.float64, device=o.device)
+    terms = torch.empty(8, dtype=torch.float32, device=o.device)
+    per_image = torch.empty(B, dtype=torch.float32, device=o.device)
+    call("mau_loss_terms", o.data_ptr(), t.data_ptr(), ws.data_ptr(), _tickets(o.device).data_ptr(), terms.data_ptr(), per_image.data_ptr(),
+         acc.data_ptr() if acc is not None else None, float(lambda_grad), float(lambda_ssim), B, C, H, W, _stream())
+    return terms, per_image
+
+
+def compute_all_loss(outputs, targets, lambda_grad=0.1, lambda_ssim=0.5, acc=None):
+    """src/utils/losses.py:101-115: the dict of all loss components (total, mse, gradient, pixel, ssim), from one launch.  The values
+    are 0-dim views of the kernel's ``terms`` and carry no gradient (this is what ``validate`` logs, never what is trained on)."""
+    terms, _ = loss_terms(outputs, targets, lambda_grad, lambda_ssim, acc)
+    return {k: terms[i] for k, i in ALL_LOSS_TERMS.items()}

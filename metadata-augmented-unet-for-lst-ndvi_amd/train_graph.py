@@ -44,6 +44,16 @@ def _make_capturable(optimizer: torch.optim.Optimizer):
                     st["step"] = st["step"].to(p.device, dtype=torch.float32)
 
 
+def _raw(t):
+    """The tensor behind an input: the packed ``Act`` a ``data.DeviceLoader`` yields as ``maps`` carries it as ``.t``."""
+    return t.t if isinstance(t, F_.Act) else t
+
+
+def _static_copy(t):
+    """A static input buffer of the graph: a clone of the tensor; an ``Act`` keeps its channel count and layout flag."""
+    return F_.Act(t.t.detach().clone(), t.C, t.nchw) if isinstance(t, F_.Act) else t.detach().clone()
+
+
 def _grad_accumulator(p: torch.Tensor):
     with torch.enable_grad():
         return p.view_as(p).grad_fn.next_functions[0][0]
@@ -72,7 +82,9 @@ class GraphedTrainStep:
     scalar tensor.  ``clip_grad_norm``: max norm of ``torch.nn.utils.clip_grad_norm_`` (src/train.py:253-254), 0 = off; an optimizer
     of ``mau_amd.optim`` takes it over as its ``max_grad_norm`` (norm and coefficient in one launch, the scaling inside the update).
     ``copy_inputs=False``: the tensors of the capturing call ARE the static buffers -- later calls must pass the same
-    tensors (a resident synthetic batch, or buffers the loader fills in place); the default copies every batch in."""
+    tensors (a resident synthetic batch, or buffers the loader fills in place); the default copies every batch in.
+    ``maps`` may be the packed ``Act`` of ``data.DeviceLoader``: the static buffer is a clone of its tensor in an ``Act`` of the same
+    channel count and layout, later batches are copied into it."""
 
     def __init__(self, model: torch.nn.Module, optimizer: torch.optim.Optimizer, criterion: Callable, warmup: int = 3,
                  clip_grad_norm: float = 0.0, copy_inputs: bool = True, grad_sync=None):
@@ -114,7 +126,7 @@ class GraphedTrainStep:
 
     def _capture(self, batch):
         if self.copy_inputs:
-            self._in = [t.detach().clone() for t in batch]
+            self._in = [_static_copy(t) for t in batch]
         else:
             self._in = list(batch)
         self.optimizer.zero_grad(set_to_none=True)        # the captured backward ASSIGNS the gradients (static buffers of the graph)
@@ -163,6 +175,21 @@ class GraphedTrainStep:
         self.graph, self.loss, self.outputs = graph, loss.detach(), outputs.detach()
 
     # ------------------------------------------------------------------ #
+    def matches(self, maps, temp_series, metadata, targets) -> bool:
+        """Whether the batch has the shapes the graph was captured for (always true before the capture)."""
+        return self._in is None or all(_raw(a).shape == _raw(b).shape for a, b in zip(self._in, (maps, temp_series, metadata, targets)))
+
+    def eager_step(self, maps, temp_series, metadata, targets):
+        """One training step OUTSIDE the graph, for a batch whose shapes differ from the captured ones (the ragged last batch of an
+        epoch, a time series padded to another length): the same model -> criterion -> backward -> clip -> optimizer.step ->
+        zero_grad sequence as the warm-up steps.  It is not counted as a call; replay resumes with the next matching batch (the
+        optimizer's step hook marks the parameters as updated, or the optimizers of optim.py leave fresh packs behind)."""
+        # after a capture every p.grad still IS the graph's static gradient buffer (the replay assigns it): an eager backward would
+        # accumulate into the last replay's gradient.  Letting go of the Python reference leaves the graph's memory where it is.
+        self.optimizer.zero_grad(set_to_none=True)
+        loss, _ = self._eager(maps, temp_series, metadata, targets)
+        return loss
+
     def __call__(self, maps, temp_series, metadata, targets):
         """One training step on the batch; returns the loss (0-dim device tensor, overwritten by the next call)."""
         self.calls += 1
@@ -174,10 +201,11 @@ class GraphedTrainStep:
             self._capture(batch)
         elif self.copy_inputs:
             for dst, src in zip(self._in, batch):
+                dst, src = _raw(dst), _raw(src)
                 if dst.shape != src.shape:
                     raise ValueError(f"GraphedTrainStep was captured for shape {tuple(dst.shape)}, got {tuple(src.shape)}")
                 dst.copy_(src, non_blocking=True)
-        elif any(a.data_ptr() != b.data_ptr() or a.shape != b.shape for a, b in zip(self._in, batch)):
+        elif any(_raw(a).data_ptr() != _raw(b).data_ptr() or _raw(a).shape != _raw(b).shape for a, b in zip(self._in, batch)):
             raise ValueError("GraphedTrainStep(copy_inputs=False): pass the tensors of the captured call (fill them in place)")
         if self._self_packing:
             # the graph holds no pack launch of its own.  If something outside changed parameters since the last replay -- another
