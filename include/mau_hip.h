@@ -498,6 +498,44 @@ int mau_scenario_result(const float* out, const float* temp_orig, const unsigned
                         double temp_std, float* ndvi, float* temp_c, float* delta, double* rows, double* ws, unsigned* tickets, int N,
                         int H, int W, mau_stream_t stream);
 
+/* ---- ground-truth sensitivity (test/generate_ground_truth_sensitivity.py): binned mean / standard deviation of the targets of a
+ *      split, TWO launches per batch, no target kept on the host.  Additive to ABI 5 ----
+ * A moment row is mau_moments_row_elems() = 4 fp64: [0] n, the number of values  [1] their mean  [2] M2 = sum (x - mean)^2
+ * [3] the number of non-finite values among them (their arithmetic propagates: a NaN value gives a NaN mean and M2, as np.mean /
+ * np.std do).  Two rows a, b merge by the pairwise update, in fp64 without contraction:
+ *   delta = mean_b - mean_a;  n = n_a + n_b;  mean = mean_a + (delta * n_b) / n;
+ *   M2 = (M2_a + M2_b) + (delta * delta) * ((n_a * n_b) / n);  an empty a (n_a == 0) gives b as it is.
+ *
+ * mau_plane_moments: x (B,C,H,W) fp32 NCHW, HW = H * W  ->  rows (B*C) x 4 fp64, row b*C + c = the moments of that plane.
+ * A workgroup owns 4096 consecutive pixels of ONE plane (mau_plane_moments_chunks(HW) workgroups per plane, a function of HW
+ * alone), keeps them in registers as doubles and makes two passes: the chunk mean, then sum (x - chunk mean)^2 -- not
+ * E[x^2] - E[x]^2.  Sums are fp64 in a fixed order; the workgroup that draws the plane's last ticket merges the chunk rows in chunk
+ * order.  A row's bits do not depend on B or on the plane's place in the batch, and repeat.  16-byte loads when HW % 4 == 0 and x
+ * is 16-byte aligned, 4-byte loads otherwise (the two forms add in different orders: keep x 16-byte aligned for bits that are a
+ * function of HW alone).  ws: fp64 workspace of mau_plane_moments_ws_elems(B, C, HW) elements; tickets: a ZEROED
+ * mau_reduce_tickets_elems() buffer (left zeroed; see mau_reduce_rows_f64).  One launch per mau_reduce_tickets_elems() planes. */
+int mau_moments_row_elems(void);
+int mau_plane_moments_chunks(int64_t HW);
+size_t mau_plane_moments_ws_elems(int B, int C, int64_t HW);
+int mau_plane_moments(const float* x, double* rows, double* ws, unsigned* tickets, int B, int C, int64_t HW, mau_stream_t stream);
+/* mau_bin_moments: merges the B*C rows of a batch into table [axes][bins][C] x 4 fp64 moment rows (DEVICE resident, zeroed by the
+ * caller before the first batch), ONE workgroup, one thread per (axis, bin, channel): axes * bins * C <= mau_bin_moments_max_entries(),
+ * axes <= 4.
+ *   meta (B, meta_pitch) fp32: the normalised metadata, meta_pitch floats from row to row;
+ *   cols_host, std_host, mean_host: HOST arrays of `axes` entries -- the metadata column of an axis and what un-normalises it:
+ *     coordinate = (double)meta[b][col] * std + mean, a separately rounded fp64 product and sum (numpy: float32 array times
+ *     np.float64 scalar);
+ *   edges: DEVICE, axes x (bins + 1) fp64, the ASCENDING bin edges of axis a at edges + a * (bins + 1).  The device cannot check
+ *     the order: the HOST does (ground_truth.BinStats), unordered edges give unspecified bins (never an access out of bounds).
+ * Bin of a sample on an axis = np.digitize's: k = the number of edges <= coordinate; kept iff 1 <= k <= bins, bin k - 1 (on an edge:
+ * the upper bin; on the last edge, beyond either end, or NaN: dropped).  A thread walks the samples in sample order and merges
+ * those of its bin into its entry -- no atomics, no tickets: the table after any sequence of batches has the bits of the table
+ * after the same samples in one batch. */
+int mau_bin_moments_max_entries(void);
+int mau_bin_moments(const double* rows, const float* meta, int meta_pitch, const int* cols_host, const double* std_host,
+                    const double* mean_host, const double* edges, double* table, int B, int C, int axes, int bins,
+                    mau_stream_t stream);
+
 /* ---- loss: F.mse_loss (src/utils/losses.py:27-39) -------------------------- */
 /* loss[0] = mean((out-tgt)^2) (fp64 accumulation, fixed order); dout (optional) = 2*(out-tgt)/n;
  * partial: fp64 workspace of mau_mse_blocks(n) elements. */

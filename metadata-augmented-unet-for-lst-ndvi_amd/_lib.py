@@ -123,6 +123,12 @@ PROTOTYPES = {
     "mau_scenario_result_chunks": (_i, [_i, _i]),
     "mau_scenario_result_ws_elems": (_sz, [_i, _i, _i]),
     "mau_scenario_result": (_i, [_p, _p, _p, _p, _d, _d, _p, _p, _p, _p, _p, _p, _i, _i, _i, _p]),
+    "mau_moments_row_elems": (_i, []),
+    "mau_plane_moments_chunks": (_i, [_i64]),
+    "mau_plane_moments_ws_elems": (_sz, [_i, _i, _i64]),
+    "mau_plane_moments": (_i, [_p, _p, _p, _p, _i, _i, _i64, _p]),
+    "mau_bin_moments_max_entries": (_i, []),
+    "mau_bin_moments": (_i, [_p, _p, _i, _p, _p, _p, _p, _p, _i, _i, _i, _i, _p]),
     "mau_mse_blocks": (_i, [_i64]),
     "mau_l1_gradient_blocks": (_i, [_i64]),
     "mau_l1_gradient_loss": (_i, [_p, _p, _p, _p, _p, _f, _f, _i, _i, _i, _i, _p]),
