@@ -536,6 +536,31 @@ int mau_bin_moments(const double* rows, const float* meta, int meta_pitch, const
                     const double* mean_host, const double* edges, double* table, int B, int C, int axes, int bins,
                     mau_stream_t stream);
 
+/* ---- dataset survey (src/utils/visualize_npz.py extract_metrics): what the per-tile CSV row needs from the pixels of a compact
+ *      batch, ONE launch, every byte read once.  Additive to ABI 5 ----
+ * cls_a, cls_b (B,H,W) uint8 class maps; cont (B,5,H,W) fp32: r, g, b, ndvi_t1, temp_t1; targets (B,2,H,W) fp32: ndvi_t2, temp_t2;
+ * HW = H * W; num_classes in [1,16] (the dataset's layout: 9).  rows (B) x mau_tile_stats_row_elems() = 106 fp64, per sample:
+ *   [0,16)   pixels of cls_a per class (0 for classes >= num_classes)     [16,32)  the same of cls_b
+ *   [32], [33]  values >= num_classes in cls_a, in cls_b
+ *   [34 + 8p, 34 + 8p + 8)  the plane row of value plane p:
+ *        +0 n   +1 mean   +2 M2 = sum (x - mean)^2   +3 min   +4 max   +5 sum |x|   +6 NaN values   +7 non-finite values
+ *     p = 0..4 the planes of cont, 5 and 6 those of targets, 7 = ndvi_t2 - ndvi_t1, 8 = temp_t2 - temp_t1: the differences of the
+ *     values as stored (normalised), formed in fp64 from the loaded floats and never written to memory.
+ * Geometry and arithmetic are mau_plane_moments': a workgroup owns 4096 consecutive pixels of ONE sample and walks its planes,
+ * values as doubles from the load on, two passes over register-resident values (chunk mean, then squared distances), sums in a
+ * fixed order; the workgroup that draws the sample's last ticket merges the chunk rows in chunk order ((n, mean, M2) by the
+ * pairwise update above; min / max / counts exactly).  A row's bits depend on the sample's own bytes only -- not on B, not on its
+ * place in the batch -- and repeat.  A NaN value is counted and propagates into mean and M2; min and max skip it (the caller sets
+ * them to NaN when +6 is not zero, as np.min does).  16-byte loads of the fp32 planes and 4-byte loads of the class maps when
+ * HW % 4 == 0, cont and targets are 16-byte and cls_a and cls_b 4-byte aligned; scalar loads otherwise (the two forms add in
+ * different orders: keep the bases aligned for bits that are a function of HW alone).  ws: fp64 workspace of
+ * mau_tile_stats_ws_elems(B, HW) elements; tickets: a ZEROED mau_reduce_tickets_elems() buffer (left zeroed; see
+ * mau_reduce_rows_f64).  One launch per mau_reduce_tickets_elems() samples. */
+int mau_tile_stats_row_elems(void);
+size_t mau_tile_stats_ws_elems(int B, int64_t HW);
+int mau_tile_stats(const unsigned char* cls_a, const unsigned char* cls_b, const float* cont, const float* targets, double* rows,
+                   double* ws, unsigned* tickets, int B, int64_t HW, int num_classes, mau_stream_t stream);
+
 /* ---- loss: F.mse_loss (src/utils/losses.py:27-39) -------------------------- */
 /* loss[0] = mean((out-tgt)^2) (fp64 accumulation, fixed order); dout (optional) = 2*(out-tgt)/n;
  * partial: fp64 workspace of mau_mse_blocks(n) elements. */

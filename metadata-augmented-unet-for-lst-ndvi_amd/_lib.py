@@ -129,6 +129,9 @@ PROTOTYPES = {
     "mau_plane_moments": (_i, [_p, _p, _p, _p, _i, _i, _i64, _p]),
     "mau_bin_moments_max_entries": (_i, []),
     "mau_bin_moments": (_i, [_p, _p, _i, _p, _p, _p, _p, _p, _i, _i, _i, _i, _p]),
+    "mau_tile_stats_row_elems": (_i, []),
+    "mau_tile_stats_ws_elems": (_sz, [_i, _i64]),
+    "mau_tile_stats": (_i, [_p, _p, _p, _p, _p, _p, _p, _i, _i64, _i, _p]),
     "mau_mse_blocks": (_i, [_i64]),
     "mau_l1_gradient_blocks": (_i, [_i64]),
     "mau_l1_gradient_loss": (_i, [_p, _p, _p, _p, _p, _f, _f, _i, _i, _i, _i, _p]),

@@ -95,14 +95,18 @@ class FuturePredictionDataset(Dataset):
 
     ``compact=True`` (default) yields a dict with the class maps as uint8 and a flip flag; ``compact=False`` yields
     the reference's 6-tuple ``(input, metadata, temp_series, t1_date, t2_date, target)`` with the transform applied on
-    the host exactly like the reference."""
+    the host exactly like the reference.
+
+    ``skip_errors=True`` (the dataset survey, ``mau_amd.dataset_metrics``): a tile that cannot be read, parsed or compacted is
+    reported as the reference's survey reports it (``Failed to process <file>: <error>``) and yields ``None``, which ``collate_fn``
+    drops; compact samples then also carry their file name (``"filepath"``)."""
 
     def __init__(self, split: str, transform=None, processed_dir: Optional[str] = None, compact: bool = True,
-                 num_classes: int = NUM_CLASSES):
+                 num_classes: int = NUM_CLASSES, skip_errors: bool = False):
         if processed_dir is None:
             processed_dir = os.environ.get("PROCESSED_IMAGE_DATASET", os.path.join("data", "processed"))
         self.processed_dir, self.split, self.transform = processed_dir, split, transform
-        self.compact, self.num_classes = compact, num_classes
+        self.compact, self.num_classes, self.skip_errors = compact, num_classes, skip_errors
         self.data_dir = os.path.join(processed_dir, split)
         if not os.path.isdir(self.data_dir):
             raise FileNotFoundError(f"Directory for split '{split}' not found at: {self.data_dir}")
@@ -117,6 +121,18 @@ class FuturePredictionDataset(Dataset):
         return (int(parts[-5]), int(parts[-4])), (int(parts[-2]), int(parts[-1].split(".")[0]))
 
     def __getitem__(self, idx):
+        if not self.skip_errors:
+            return self._load(idx)
+        try:
+            sample = self._load(idx)
+        except Exception as e:                               # visualize_npz.py:863-868
+            print(f"Failed to process {self.file_list[idx]}: {e}")
+            return None
+        if self.compact:
+            sample["filepath"] = os.path.basename(self.file_list[idx])
+        return sample
+
+    def _load(self, idx):
         filepath = self.file_list[idx]
         (t1y, t1m), (t2y, t2m) = self._dates(filepath)
         data = np.load(filepath)
