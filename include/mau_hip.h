@@ -317,6 +317,19 @@ int mau_resize_bilinear_bn_fwd(const void* y, int ldy, int h, int w, const float
 /* dsrc (N,h,w,C) = adjoint of the above applied to ddst[..., choff:choff+C] (gather form, no atomics). */
 int mau_resize_bilinear_bwd(const void* ddst, int ldddst, int choff, int H, int W, void* dsrc, int lddsrc,
                             int dtype, int N, int h, int w, int C, mau_stream_t stream);
+/* Which kernels such a resize runs (host-only query, no launch; diagnostics and tests: "did this shape reach the path it is meant
+ * to?"), written to HOST ints, any of which may be NULL.  The launchers above read the same plan.
+ * fwd_kernel: MAU_RESIZE_FWD_ROWCOL (h <= H, w <= W and at most 3 destination columns per source column, whatever the height ratio,
+ * h = 1 included: a column of fwd_rows source cells per thread), MAU_RESIZE_FWD_CELL (any other h <= H, w <= W: one source cell per
+ * thread), MAU_RESIZE_FWD_DEST (h > H or w > W: one destination pixel per thread).  fwd_rows: source rows per workgroup (8, 4, 2 or 1 by how many
+ * workgroups the launch has; 1 for the other kernels).  bwd_kernel: MAU_RESIZE_BWD_2X2 (adjoint of an upsampling with h, w >= 2)
+ * or MAU_RESIZE_BWD_GATHER. */
+#define MAU_RESIZE_FWD_ROWCOL 0
+#define MAU_RESIZE_FWD_CELL 1
+#define MAU_RESIZE_FWD_DEST 2
+#define MAU_RESIZE_BWD_2X2 0
+#define MAU_RESIZE_BWD_GATHER 1
+int mau_resize_bilinear_plan(int N, int h, int w, int H, int W, int C, int* fwd_kernel_host, int* fwd_rows_host, int* bwd_kernel_host);
 /* dst[..., choff:choff+C] = src[..., :C]  (channel concat building block, src/model.py:279-282);
  * also zero-fills dst channels [choff+C, zero_to) when zero_to > choff+C. */
 int mau_copy_channels(const void* src, int ldsrc, void* dst, int lddst, int choff, int zero_to, int dtype,

@@ -81,6 +81,7 @@ PROTOTYPES = {
     "mau_maxpool2x2_bwd_add": (_i, [_p, _i, _p, _i, _p, _i, _p, _i, _i, _i, _i, _i, _i, _p]),
     "mau_resize_bilinear_fwd": (_i, [_p, _i, _i, _i, _p, _i, _i, _i, _i, _i, _i, _i, _p]),
     "mau_resize_bilinear_bwd": (_i, [_p, _i, _i, _i, _i, _p, _i, _i, _i, _i, _i, _i, _p]),
+    "mau_resize_bilinear_plan": (_i, [_i, _i, _i, _i, _i, _i, _p, _p, _p]),
     "mau_copy_channels": (_i, [_p, _i, _p, _i, _i, _i, _i, _i64, _i, _p]),
     "mau_bcast_fill": (_i, [_p, _p, _i, _i, _i, _i, _i, _i, _i, _p]),
     "mau_bcast_bwd_ws_elems": (_sz, [_i, _i, _i]),
@@ -179,6 +180,17 @@ def conv3x3_variant(dtype: int, N: int, H: int, W: int, Cout: int, Cin: int = 0)
     th, nw, bn, kg = C.c_int(), C.c_int(), C.c_int(), C.c_int()
     check(lib.mau_conv3x3_variant(dtype, N, H, W, Cin, Cout, C.byref(th), C.byref(nw), C.byref(bn), C.byref(kg)), "mau_conv3x3_variant")
     return th.value, nw.value, bn.value, kg.value
+
+
+RESIZE_FWD_ROWCOL, RESIZE_FWD_CELL, RESIZE_FWD_DEST = 0, 1, 2
+RESIZE_BWD_2X2, RESIZE_BWD_GATHER = 0, 1
+
+
+def resize_bilinear_plan(N: int, h: int, w: int, H: int, W: int, channels: int):
+    """(forward kernel, source rows per workgroup of the row-column kernel, backward kernel) such a resize runs (host query)."""
+    fk, fr, bk = C.c_int(), C.c_int(), C.c_int()
+    check(lib.mau_resize_bilinear_plan(N, h, w, H, W, channels, C.byref(fk), C.byref(fr), C.byref(bk)), "mau_resize_bilinear_plan")
+    return fk.value, fr.value, bk.value
 
 
 def call(name: str, *args):

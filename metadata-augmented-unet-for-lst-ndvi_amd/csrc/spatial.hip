@@ -784,22 +784,52 @@ static bool resize_rows_ok(int h, int w, int H, int W) {
   return h <= H && w <= W && h <= 65535 && resize_max_cols_per_cell(w, W) <= 3;
 }
 
+// The one place where the resize kernels are chosen (forward: row-column / per-cell / per-destination and the source rows RY per
+// workgroup of the row-column kernel; backward: 2x2 blocks or the gather form): the three launchers below and the query
+// mau_resize_bilinear_plan read it, so what a test asserts about a shape is what the launch does.
+struct ResizePlan {
+  int fwd, rows, bwd;
+};
+static ResizePlan resize_plan(int N, int h, int w, int H, int W, int C) {
+  ResizePlan p{MAU_RESIZE_FWD_DEST, 1, MAU_RESIZE_BWD_GATHER};
+  const int C8 = round_up(C, 8);
+  if (resize_rows_ok(h, w, H, W)) {                    // upsampling by <= ~2: a column of source cells per thread
+    const int xb = ceil_div(w * (C8 / 8), 256);
+    int RY = 8;
+    while (RY > 1 && (int64_t)xb * ceil_div(h, RY) * N < 1024) RY >>= 1;
+    p.fwd = MAU_RESIZE_FWD_ROWCOL;
+    p.rows = RY;
+  } else if (h <= H && w <= W && h <= 65535) {         // any other upsampling: one thread per source cell
+    p.fwd = MAU_RESIZE_FWD_CELL;
+  }
+  if (h <= H && w <= W && h >= 2 && w >= 2) p.bwd = MAU_RESIZE_BWD_2X2;      // adjoint of an upsampling: 2x2 source pixels per thread
+  return p;
+}
+
+int mau_resize_bilinear_plan(int N, int h, int w, int H, int W, int C, int* fwd_kernel_host, int* fwd_rows_host, int* bwd_kernel_host) {
+  MAU_REQUIRE(N > 0 && h > 0 && w > 0 && H > 0 && W > 0 && C > 0, "resize_bilinear_plan: bad arguments");
+  const ResizePlan p = resize_plan(N, h, w, H, W, C);
+  if (fwd_kernel_host) *fwd_kernel_host = p.fwd;
+  if (fwd_rows_host) *fwd_rows_host = p.rows;
+  if (bwd_kernel_host) *bwd_kernel_host = p.bwd;
+  return MAU_OK;
+}
+
 int mau_resize_bilinear_fwd(const void* src, int ldsrc, int h, int w, void* dst, int lddst, int choff, int dtype, int N,
                             int H, int W, int C, mau_stream_t stream) {
   MAU_REQUIRE(src && dst && N > 0 && h > 0 && w > 0 && H > 0 && W > 0 && C > 0, "resize_bilinear_fwd: bad arguments");
   const int C8 = round_up(C, 8);
   MAU_REQUIRE(ldsrc % 8 == 0 && lddst % 8 == 0 && choff % 8 == 0 && ldsrc >= C8 && lddst >= choff + C8, "resize_bilinear_fwd: bad ld/choff");
   MAU_REQUIRE(H <= 65535 && N <= 65535, "resize_bilinear_fwd: H and N must fit a grid dimension");
-  if (resize_rows_ok(h, w, H, W)) {                    // upsampling by <= ~2: a column of source cells per thread
-    const int xb = ceil_div(w * (C8 / 8), 256);
-    int RY = 8;
-    while (RY > 1 && (int64_t)xb * ceil_div(h, RY) * N < 1024) RY >>= 1;
-    dim3 gridr(xb, ceil_div(h, RY), N);
+  const ResizePlan plan = resize_plan(N, h, w, H, W, C);
+  if (plan.fwd == MAU_RESIZE_FWD_ROWCOL) {
+    const int RY = plan.rows;
+    dim3 gridr(ceil_div(w * (C8 / 8), 256), ceil_div(h, RY), N);
     MAU_DISPATCH_DTYPE(dtype, MAU_LAUNCH((resize_rows_kernel<T, false>), gridr, dim3(256), 0, (hipStream_t)stream, (const T*)src, ldsrc, h, w, (T*)dst, lddst, choff,
                                          H, W, C8, (const float*)nullptr, (const float*)nullptr, C, RY));
     return check_launch("resize_rows_kernel");
   }
-  if (h <= H && w <= W && h <= 65535) {                // any other upsampling: one thread per source cell
+  if (plan.fwd == MAU_RESIZE_FWD_CELL) {
     dim3 gridc(ceil_div(w * (C8 / 8), 256), h, N);
     MAU_DISPATCH_DTYPE(dtype, MAU_LAUNCH((resize_fwd_cell_kernel<T, false>), gridc, dim3(256), 0, (hipStream_t)stream, (const T*)src, ldsrc, h, w, (T*)dst, lddst, choff, H, W, C8,
                                          (const float*)nullptr, (const float*)nullptr, C));
@@ -816,11 +846,10 @@ int mau_resize_bilinear_bn_fwd(const void* y, int ldy, int h, int w, const float
   MAU_REQUIRE(h <= H && w <= W && h <= 65535 && N <= 65535, "resize_bilinear_bn_fwd: an upsampling (h <= H, w <= W), h and N within a grid dimension");
   const int C8 = round_up(C, 8);
   MAU_REQUIRE(ldy % 8 == 0 && lddst % 8 == 0 && choff % 8 == 0 && ldy >= C8 && lddst >= choff + C8, "resize_bilinear_bn_fwd: bad ld/choff");
-  if (resize_rows_ok(h, w, H, W)) {                    // upsampling by <= ~2: a column of source cells per thread
-    const int xb = ceil_div(w * (C8 / 8), 256);
-    int RY = 8;
-    while (RY > 1 && (int64_t)xb * ceil_div(h, RY) * N < 1024) RY >>= 1;
-    dim3 gridr(xb, ceil_div(h, RY), N);
+  const ResizePlan plan = resize_plan(N, h, w, H, W, C);      // an upsampling: row-column or per-cell, never per-destination
+  if (plan.fwd == MAU_RESIZE_FWD_ROWCOL) {
+    const int RY = plan.rows;
+    dim3 gridr(ceil_div(w * (C8 / 8), 256), ceil_div(h, RY), N);
     MAU_DISPATCH_DTYPE(dtype, MAU_LAUNCH((resize_rows_kernel<T, true>), gridr, dim3(256), 0, (hipStream_t)stream, (const T*)y, ldy, h, w, (T*)dst, lddst, choff, H,
                                          W, C8, scale, shift, C, RY));
     return check_launch("resize_rows_kernel<BN>");
@@ -837,7 +866,7 @@ int mau_resize_bilinear_bwd(const void* ddst, int ldddst, int choff, int H, int 
   const int C8 = round_up(C, 8);
   MAU_REQUIRE(ldddst % 8 == 0 && lddsrc % 8 == 0 && choff % 8 == 0 && lddsrc >= C8 && ldddst >= choff + C8, "resize_bilinear_bwd: bad ld/choff");
   MAU_REQUIRE(h <= 65535 && N <= 65535, "resize_bilinear_bwd: h and N must fit a grid dimension");
-  if (h <= H && w <= W && h >= 2 && w >= 2) {          // adjoint of an upsampling: 2x2 source pixels per thread
+  if (resize_plan(N, h, w, H, W, C).bwd == MAU_RESIZE_BWD_2X2) {
     dim3 grid2(ceil_div(((w + 1) / 2) * (C8 / 8), 256), (h + 1) / 2, N);
     MAU_DISPATCH_DTYPE(dtype, MAU_LAUNCH(resize_bwd2_kernel<T>, grid2, dim3(256), 0, (hipStream_t)stream, (const T*)ddst, ldddst, choff, H, W, (T*)dsrc, lddsrc, h, w, C8));
     return check_launch("resize_bwd2_kernel");
@@ -851,7 +880,10 @@ int mau_copy_channels(const void* src, int ldsrc, void* dst, int lddst, int chof
                       int C, mau_stream_t stream) {
   MAU_REQUIRE(src && dst && npix > 0 && C > 0 && ldsrc >= C && lddst >= choff + C && zero_to <= lddst, "copy_channels: bad arguments");
   hipStream_t st = (hipStream_t)stream;
-  const bool vec = (C % 8 == 0) && (choff % 8 == 0) && (ldsrc % 8 == 0) && (lddst % 8 == 0) && zero_to <= choff + C;
+  // (16-byte vector accesses: a caller may pass a pointer advanced by a channel offset that is no multiple of 8 -- the element
+  //  kernel is correct at any alignment)
+  const bool vec = (C % 8 == 0) && (choff % 8 == 0) && (ldsrc % 8 == 0) && (lddst % 8 == 0) && zero_to <= choff + C &&
+                   ((uintptr_t)src % 16) == 0 && ((uintptr_t)dst % 16) == 0;
   if (vec) {
     const int nv = C / 8, nvl = nv < 256 ? nv : 256;
     const int pixb = (256 / nvl) * 8;
