@@ -3,35 +3,37 @@
 // Everything a row of the reference's test/evaluate.py holds is a sum over the pixels of (prediction, target, class id):
 //   overall MAE / RMSE, MAE / RMSE and pixel count per class, the population variance of the 5-point Laplacian of both
 //   maps (scipy.ndimage.laplace, boundary mode 'reflect': the edge sample repeated), non-finite counts and min / max.
-// Grid (row chunks, (sample, channel) rows): a workgroup owns EVAL_CHUNK_PIX / W (at least one) consecutive image rows of ONE
+// Grid (row chunks, (sample, channel) rows): a workgroup owns CHUNK_PIX / W (at least one) consecutive image rows of ONE
 // map -- the chunking is a function of (H, W) alone.  Every value becomes a double as it is loaded, p = out * scale + shift
-// and g = tgt * scale + shift are fp64 products and sums without contraction, and every sum is fp64 in a fixed order:
-// a thread adds its pixels in index order, a wave joins its lanes by an xor butterfly (every lane computes the same tree),
-// the four waves are added in wave order, and the workgroup that draws the row's last ticket (last_block_of) adds the
-// row's chunk partials in chunk order and writes the finished row.  A row's bits depend on nothing but its own maps.
+// and g = tgt * scale + shift are fp64 products and sums without contraction, and every sum is fp64 in the fixed order of
+// chunk_reduce.h: a thread adds its pixels in index order, block_join makes the chunk's partial row, and the workgroup that
+// draws the row's last ticket joins the partial rows in chunk order (chunk_join) and writes the finished row.  A row's bits
+// depend on nothing but its own maps.
 // The class sums are kept in registers: bin k takes `cls == k ? value : 0`, one select per bin and pixel, so that no
 // accumulator is indexed dynamically (fp64 rate is not what limits a kernel that reads 9 bytes per pixel).
 #include <math.h>
-#include "mau_common.h"
+#include "chunk_reduce.h"
 
 #pragma clang fp contract(off)
 
 namespace mau {
 
-constexpr int EVAL_CHUNK_PIX = 4096;     // pixels of a workgroup's run of image rows (250 x 250: 16 rows, 16 chunks per map)
 constexpr int EVAL_MAX_CLS = 16;
 constexpr int EVAL_HEAD = 11;            // row entries in front of the per-class blocks (include/mau_hip.h)
 // per-thread accumulators: 0 sum|d| 1 sum d^2 2,3 sum / sum of squares of lap(p) 4,5 of lap(g) 6,7 non-finite out / tgt
 // 8 min p 9 max p 10 min g 11 max g, then NB counts, NB sums |d|, NB sums d^2 (bin NB-1: class ids >= ncls)
 constexpr int EVAL_ACC0 = 12;
 
-static inline int eval_rows_per_chunk(int W) { return W >= EVAL_CHUNK_PIX ? 1 : EVAL_CHUNK_PIX / W; }
+// image rows of a workgroup: a run of at most CHUNK_PIX pixels (250 x 250: 16 rows, 16 chunks per map)
+static inline int eval_rows_per_chunk(int W) { return W >= CHUNK_PIX ? 1 : CHUNK_PIX / W; }
 static inline int eval_chunks(int H, int W) { return ceil_div(H, eval_rows_per_chunk(W)); }
 static inline int eval_bins(int ncls) { return ncls <= 9 ? 10 : EVAL_MAX_CLS + 1; }
 
-__device__ __forceinline__ double eval_join(int v, double a, double b) {
-  return (v == 8 || v == 10) ? fmin(a, b) : (v == 9 || v == 11) ? fmax(a, b) : a + b;
-}
+struct EvalJoin {
+  __device__ __forceinline__ double operator()(int v, double a, double b) const {
+    return (v == 8 || v == 10) ? fmin(a, b) : (v == 9 || v == 11) ? fmax(a, b) : a + b;
+  }
+};
 
 template <int NB>
 __global__ __launch_bounds__(256) void eval_metrics_kernel(const float* __restrict__ out, const float* __restrict__ tgt,
@@ -95,34 +97,12 @@ __global__ __launch_bounds__(256) void eval_metrics_kernel(const float* __restri
     }
   }
 
-  // lanes of a wave: xor butterfly (addition, fmin and fmax commute: every lane ends with the same bits)
-#pragma unroll
-  for (int v = 0; v < NV; ++v) {
-#pragma unroll
-    for (int s = 32; s >= 1; s >>= 1) acc[v] = eval_join(v, acc[v], __shfl_xor(acc[v], s, 64));
-  }
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  if (lane == 0) {
-#pragma unroll
-    for (int v = 0; v < NV; ++v) wsum[wave][v] = acc[v];
-  }
-  __syncthreads();
   double* prow = part + (size_t)blockIdx.y * chunks * NV;
-  if (threadIdx.x < NV) {
-    const int v = threadIdx.x;
-    double s = wsum[0][v];
-    for (int w = 1; w < 4; ++w) s = eval_join(v, s, wsum[w][v]);
-    prow[(size_t)blockIdx.x * NV + v] = s;
-  }
+  block_join<NV>(acc, wsum, EvalJoin(), prow + (size_t)blockIdx.x * NV);
   if (!last_block_of(tickets + blockIdx.y, (unsigned)chunks)) return;
 
   // level 2: the row's chunk partials in chunk order, then the finished row
-  if (threadIdx.x < NV) {
-    const int v = threadIdx.x;
-    double s = prow[v];
-    for (int n = 1; n < chunks; ++n) s = eval_join(v, s, prow[(size_t)n * NV + v]);
-    tot[v] = s;
-  }
+  if (threadIdx.x < NV) tot[threadIdx.x] = chunk_join(prow, chunks, NV, threadIdx.x, EvalJoin());
   __syncthreads();
   const int relems = EVAL_HEAD + 3 * ncls;
   double* r = rows + (size_t)row * relems;
@@ -164,10 +144,7 @@ int mau_eval_metrics_chunks(int H, int W) { return H > 0 && W > 0 ? eval_chunks(
 
 size_t mau_eval_metrics_ws_elems(int B, int C, int H, int W, int ncls) {
   if (B <= 0 || C <= 0 || H <= 0 || W <= 0 || ncls < 1 || ncls > EVAL_MAX_CLS) return 0;
-  // the launches of one call reuse the partials of the first mau_reduce_tickets_elems() rows
-  const int64_t nrows = (int64_t)B * C;
-  const int per = mau_reduce_tickets_elems();
-  return (size_t)(nrows < per ? nrows : per) * eval_chunks(H, W) * (EVAL_ACC0 + 3 * eval_bins(ncls));
+  return (size_t)ticket_ws_rows((int64_t)B * C) * eval_chunks(H, W) * (EVAL_ACC0 + 3 * eval_bins(ncls));
 }
 
 int mau_eval_metrics(const float* out, const float* tgt, const unsigned char* cls, const double* scale, const double* shift,
@@ -178,19 +155,15 @@ int mau_eval_metrics(const float* out, const float* tgt, const unsigned char* cl
   MAU_REQUIRE((int64_t)H * W <= (1 << 30), "eval_metrics: maps of at most 2^30 pixels");
   MAU_REQUIRE((int64_t)B * C <= (1 << 30), "eval_metrics: at most 2^30 (sample, channel) rows");
   const int rpc = eval_rows_per_chunk(W), chunks = eval_chunks(H, W);
-  const int nrows = B * C;
-  // one ticket per (sample, channel) row: mau_reduce_tickets_elems() rows per launch
-  const int per = mau_reduce_tickets_elems();
-  for (int row0 = 0; row0 < nrows; row0 += per) {
-    const int nn = nrows - row0 < per ? nrows - row0 : per;
+  const dim3 block(256);
+  const hipStream_t st = (hipStream_t)stream;
+  return for_ticket_rows(B * C, "eval_metrics_kernel", [&](int row0, int nn) {
+    const dim3 grid(chunks, nn);
     if (eval_bins(ncls) == 10)
-      MAU_LAUNCH(eval_metrics_kernel<10>, dim3(chunks, nn), dim3(256), 0, (hipStream_t)stream, out, tgt, cls, scale, shift, ws, tickets, rows, C, H, W, ncls, rpc, row0);
+      MAU_LAUNCH(eval_metrics_kernel<10>, grid, block, 0, st, out, tgt, cls, scale, shift, ws, tickets, rows, C, H, W, ncls, rpc, row0);
     else
-      MAU_LAUNCH(eval_metrics_kernel<EVAL_MAX_CLS + 1>, dim3(chunks, nn), dim3(256), 0, (hipStream_t)stream, out, tgt, cls, scale, shift, ws, tickets, rows, C, H, W, ncls, rpc, row0);
-    const int st = check_launch("eval_metrics_kernel");
-    if (st != 0) return st;
-  }
-  return 0;
+      MAU_LAUNCH(eval_metrics_kernel<EVAL_MAX_CLS + 1>, grid, block, 0, st, out, tgt, cls, scale, shift, ws, tickets, rows, C, H, W, ncls, rpc, row0);
+  });
 }
 
 }  // extern "C"

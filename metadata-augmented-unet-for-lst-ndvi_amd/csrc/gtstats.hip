@@ -3,102 +3,46 @@
 //   plane_moments_kernel  (B,C,H,W) fp32 -> per (sample, channel) plane the moment row (n, mean, M2 = sum (x - mean)^2, non-finite);
 //   bin_moments_kernel    the B*C rows of a batch merged into a device-resident table [axes][bins][C] of such rows.
 //
-// plane moments: grid (chunks of GT_CHUNK_PIX consecutive pixels of ONE plane, planes) as scenario_result_kernel -- the chunking is
-// a function of H * W alone.  A workgroup keeps its <= 16 values per thread in registers, as doubles from the load on, and makes
-// two passes over them: the chunk mean, then sum (x - chunk mean)^2.  (Not E[x^2] - E[x]^2: a temperature in physical units has
-// |mean| >> std, where the one-pass form loses half its digits.)  Sums are fp64 in a fixed order: a thread adds its values in slot
-// order, a wave joins its lanes by an xor butterfly, the four waves are added in wave order, and the workgroup that draws the
-// plane's last ticket (last_block_of) merges the chunk partials IN CHUNK ORDER with the pairwise update (moment_merge).  A row's
-// bits depend on nothing but its own plane.  A non-finite value is counted and its arithmetic left to propagate (a NaN pixel
-// gives a NaN mean and M2, as np.mean / np.std do).
+// plane moments: grid (chunks of CHUNK_PIX consecutive pixels of ONE plane, planes) -- the chunking is a function of H * W alone.
+// Loader, two-pass moments and the fixed order of every sum are chunk_reduce.h's: a workgroup keeps its <= 16 values per thread
+// in registers, as doubles from the load on (load_plane), chunk_moments makes the chunk's moment row (a temperature in physical
+// units has |mean| >> std: two passes), and the workgroup that draws the plane's last ticket merges the chunk rows IN CHUNK ORDER
+// with the pairwise update (merge_chunks).  A row's bits depend on nothing but its own plane.  A non-finite value is counted
+// and its arithmetic left to propagate (a NaN pixel gives a NaN mean and M2, as np.mean / np.std do).
 //
 // bin moments: one workgroup, one thread per (axis, bin, channel).  The bin of every (axis, sample) is np.digitize's (the number
 // of edges <= x) and is staged in LDS; a thread then walks the samples IN SAMPLE ORDER and merges those of its bin into its table
 // entry with the same update.  No atomics, no tickets: the table after any sequence of batches has the bits of the table after
 // the same samples in one batch.
 #include <math.h>
-#include "mau_common.h"
-#include "moments.h"       // Moments, moment_merge, block_sum: shared with tilestats.hip
+#include "chunk_reduce.h"
 
 #pragma clang fp contract(off)
 
 namespace mau {
 
-constexpr int GT_CHUNK_PIX = 4096;       // 250 x 250: 16 chunks per plane; 16 values per thread
-constexpr int GT_SLOTS = GT_CHUNK_PIX / 256;
 constexpr int GT_ROW = 4;                // n, mean, M2, non-finite values
 constexpr int GT_MAX_AXES = 4;
 constexpr int GT_MAX_THREADS = 1024;     // (axis, bin, channel) entries of a table: one workgroup
 constexpr int GT_TILE = 1024;            // samples whose bins are staged in LDS at a time
 
-static inline int gt_chunks(int64_t HW) { return ceil_div(HW, GT_CHUNK_PIX); }
-
-// VEC4 (H * W a multiple of 4 and a 16-byte aligned tensor: every plane and chunk base is then 16-byte aligned): slot 4k + j of
-// thread t is pixel (k * 256 + t) * 4 + j of the chunk, one 16-byte load per k.  Otherwise slot k is pixel k * 256 + t, 4-byte
-// coalesced loads.  A slot beyond the (partial, last) chunk loads pixel 0 of the chunk -- no exec-masked load -- and counts as 0.
 template <bool VEC4>
 __global__ __launch_bounds__(256) void plane_moments_kernel(const float* __restrict__ x, double* part, unsigned* tickets,
                                                             double* __restrict__ rows, int64_t HW, int row0) {
-  __shared__ double wsum[3][4];
+  __shared__ double sm[4];
+  __shared__ double sr[4][2];
   const int plane = row0 + blockIdx.y, chunks = gridDim.x;
-  const int64_t q0 = (int64_t)blockIdx.x * GT_CHUNK_PIX;
-  const int npx = (int)(HW - q0 < GT_CHUNK_PIX ? HW - q0 : GT_CHUNK_PIX);
-  const float* pc = x + (size_t)plane * HW + q0;
-
-  double v[GT_SLOTS];
-  bool ok[GT_SLOTS];
-  double bad = 0.0;
-  if (VEC4) {
-#pragma unroll
-    for (int k = 0; k < GT_SLOTS / 4; ++k) {
-      const int idx = (k * 256 + (int)threadIdx.x) * 4;
-      const bool in = idx < npx;                          // npx is a multiple of 4 here: the whole quad is inside or outside
-      const f32x4 f = *reinterpret_cast<const f32x4*>(pc + (in ? idx : 0));
-#pragma unroll
-      for (int j = 0; j < 4; ++j) {
-        ok[4 * k + j] = in;
-        v[4 * k + j] = in ? (double)f[j] : 0.0;
-        bad += in && !isfinite(f[j]) ? 1.0 : 0.0;
-      }
-    }
-  } else {
-#pragma unroll
-    for (int k = 0; k < GT_SLOTS; ++k) {
-      const int idx = k * 256 + (int)threadIdx.x;
-      const bool in = idx < npx;
-      const float f = pc[in ? idx : 0];
-      ok[k] = in;
-      v[k] = in ? (double)f : 0.0;
-      bad += in && !isfinite(f) ? 1.0 : 0.0;
-    }
-  }
-
-  // pass one: the chunk mean
-  double s = 0.0;
-#pragma unroll
-  for (int k = 0; k < GT_SLOTS; ++k) s += v[k];
-  const double n = (double)npx;
-  const double mean = block_sum(s, wsum[0]) / n;
-  bad = block_sum(bad, wsum[1]);
-  // pass two: the squared distances to it
-  double q = 0.0;
-#pragma unroll
-  for (int k = 0; k < GT_SLOTS; ++k) {
-    const double d = v[k] - mean;
-    q += ok[k] ? d * d : 0.0;
-  }
-  const double m2 = block_sum(q, wsum[2]);
-
+  const int64_t q0 = (int64_t)blockIdx.x * CHUNK_PIX;
+  const int npx = (int)(HW - q0 < CHUNK_PIX ? HW - q0 : CHUNK_PIX);
+  const unsigned ok = slot_mask<VEC4>(npx);
+  double v[CHUNK_SLOTS];
+  load_plane<VEC4>(x + (size_t)plane * HW + q0, ok, v);
   double* prow = part + (size_t)blockIdx.y * chunks * GT_ROW;
-  if (threadIdx.x == 0) moment_store(prow + (size_t)blockIdx.x * GT_ROW, Moments{n, mean, m2, bad});
+  chunk_moments<false>(v, ok, (double)npx, sm, sr, prow + (size_t)blockIdx.x * GT_ROW);
   if (!last_block_of(tickets + blockIdx.y, (unsigned)chunks)) return;
 
-  // level 2: the plane's chunk partials in chunk order, then the finished row
-  if (threadIdx.x == 0) {
-    Moments acc = moment_load(prow);
-    for (int c = 1; c < chunks; ++c) acc = moment_merge(acc, moment_load(prow + (size_t)c * GT_ROW));
-    moment_store(rows + (size_t)plane * GT_ROW, acc);
-  }
+  // level 2: the plane's chunk rows in chunk order, then the finished row
+  if (threadIdx.x == 0) moment_store(rows + (size_t)plane * GT_ROW, merge_chunks(prow, chunks, GT_ROW));
 }
 
 struct BinAxes {
@@ -149,14 +93,11 @@ extern "C" {
 
 int mau_moments_row_elems(void) { return GT_ROW; }
 
-int mau_plane_moments_chunks(int64_t HW) { return HW > 0 && HW <= (1 << 30) ? gt_chunks(HW) : 0; }
+int mau_plane_moments_chunks(int64_t HW) { return HW > 0 && HW <= (1 << 30) ? chunks_of(HW) : 0; }
 
 size_t mau_plane_moments_ws_elems(int B, int C, int64_t HW) {
   if (B <= 0 || C <= 0 || HW <= 0 || HW > (1 << 30)) return 0;
-  // the launches of one call reuse the partials of the first mau_reduce_tickets_elems() planes
-  const int64_t planes = (int64_t)B * C;
-  const int per = mau_reduce_tickets_elems();
-  return (size_t)(planes < per ? planes : per) * gt_chunks(HW) * GT_ROW;
+  return (size_t)ticket_ws_rows((int64_t)B * C) * chunks_of(HW) * GT_ROW;
 }
 
 int mau_plane_moments(const float* x, double* rows, double* ws, unsigned* tickets, int B, int C, int64_t HW, mau_stream_t stream) {
@@ -165,21 +106,14 @@ int mau_plane_moments(const float* x, double* rows, double* ws, unsigned* ticket
   MAU_REQUIRE(HW <= (1 << 30), "plane_moments: planes of at most 2^30 pixels");
   MAU_REQUIRE((int64_t)B * C <= (1 << 30), "plane_moments: at most 2^30 planes");
   MAU_REQUIRE((uintptr_t)x % 4 == 0, "plane_moments: x must be 4-byte aligned");
-  const int chunks = gt_chunks(HW);
-  const int planes = B * C;
+  const int chunks = chunks_of(HW);
   const bool vec4 = HW % 4 == 0 && (uintptr_t)x % 16 == 0;
-  // one ticket per plane: mau_reduce_tickets_elems() planes per launch
-  const int per = mau_reduce_tickets_elems();
-  for (int row0 = 0; row0 < planes; row0 += per) {
-    const int nn = planes - row0 < per ? planes - row0 : per;
+  return for_ticket_rows(B * C, "plane_moments_kernel", [&](int row0, int nn) {
     if (vec4)
       MAU_LAUNCH(plane_moments_kernel<true>, dim3(chunks, nn), dim3(256), 0, (hipStream_t)stream, x, ws, tickets, rows, HW, row0);
     else
       MAU_LAUNCH(plane_moments_kernel<false>, dim3(chunks, nn), dim3(256), 0, (hipStream_t)stream, x, ws, tickets, rows, HW, row0);
-    const int st = check_launch("plane_moments_kernel");
-    if (st != 0) return st;
-  }
-  return 0;
+  });
 }
 
 int mau_bin_moments_max_entries(void) { return GT_MAX_THREADS; }

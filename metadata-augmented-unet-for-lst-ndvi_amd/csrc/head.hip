@@ -1,7 +1,7 @@
 // head.hip -- output head (1x1 conv + tanh on channel 0, reference src/model.py:241,284-292 and
 // :187-193), MetadataEncoder MLP (:38-48) and the MSE criterion (src/utils/losses.py:27-39).
 // The head reads NHWC-ld activations and writes the module's NCHW fp32 output directly.
-#include "mau_common.h"
+#include "chunk_reduce.h"
 
 namespace mau {
 
@@ -469,15 +469,10 @@ int mau_head_mean(const void* a, int lda, const float* w, const float* b, const 
   MAU_REQUIRE(lda % 8 == 0 && lda >= round_up(C, 8), "head_mean: bad ld");
   MAU_REQUIRE(HW <= (1 << 30), "head_mean: images of at most 2^30 pixels");
   const int bps = ceil_div(HW, HEAD_MEAN_PIX);
-  // one ticket per sample: mau_reduce_tickets_elems() samples per launch (the sweeps run 50 at a time: one launch)
-  const int per = mau_reduce_tickets_elems();
-  for (int n0 = 0; n0 < N; n0 += per) {
-    const int nn = N - n0 < per ? N - n0 : per;
-    MAU_DISPATCH_DTYPE(dtype, MAU_LAUNCH(head_mean_kernel<T>, dim3(bps, nn), dim3(256), 0, (hipStream_t)stream, (const T*)a, lda, w, b, scale, shift, ws, tickets, means, tanh0, HW, C, Co, n0));
-    const int st = check_launch("head_mean_kernel");
-    if (st != 0) return st;
-  }
-  return 0;
+  // one ticket per sample (the sweeps run 50 at a time: one launch)
+  MAU_DISPATCH_DTYPE(dtype, return for_ticket_rows(N, "head_mean_kernel", [&](int n0, int nn) {
+    MAU_LAUNCH(head_mean_kernel<T>, dim3(bps, nn), dim3(256), 0, (hipStream_t)stream, (const T*)a, lda, w, b, scale, shift, ws, tickets, means, tanh0, HW, C, Co, n0);
+  }));
 }
 
 int mau_head_bwd_rows(int N, int HW) { return ceil_div((int64_t)N * HW, HEAD_PIX_PER_BLOCK); }

@@ -10,13 +10,13 @@
 // continuous planes are normalised in fp64 with IEEE division and rounded to float once: the bits of the reference's float64
 // numpy followed by .float().  A table entry outside the canvas is clamped (no read outside the buffer).
 //
-// result: a workgroup owns SCN_CHUNK_PIX consecutive pixels of ONE scenario -- the chunking is a function of H * W alone.  The
+// result: a workgroup owns CHUNK_PIX consecutive pixels of ONE scenario -- the chunking is a function of H * W alone.  The
 // temperature is two separately rounded fp32 operations (numpy on a float32 array with Python-float scalars).  Sums are fp64 in
-// a fixed order, as evalmetrics.hip: a thread adds its pixels in index order, a wave joins its lanes by an xor butterfly, the four
-// waves are added in wave order, and the workgroup that draws the scenario's last ticket (last_block_of) adds the chunk partials
-// in chunk order.  No float atomics; a row's bits depend on nothing but its own scenario.
+// the fixed order of chunk_reduce.h: a thread adds its pixels in index order, block_join makes the chunk's partial row, and the
+// workgroup that draws the scenario's last ticket joins the partial rows in chunk order (chunk_join).  No float atomics; a row's
+// bits depend on nothing but its own scenario.
 #include <math.h>
-#include "mau_common.h"
+#include "chunk_reduce.h"
 
 #pragma clang fp contract(off)
 
@@ -24,12 +24,9 @@ namespace mau {
 
 constexpr int SCN_MAX_CLS = 16;
 constexpr int SCN_NCONT = 5;             // rgb (3) + ndvi + temperature
-constexpr int SCN_CHUNK_PIX = 4096;      // 512 x 512: 64 chunks per scenario; 16 pixels per thread
 constexpr int SCN_ROW = 5;               // mean, min, max of the difference, edited pixels, mean of the difference over them
 // per-thread accumulators: 0 sum d  1 min d  2 max d  3 edited pixels  4 sum d over edited pixels
 constexpr int SCN_NV = 5;
-
-static inline int scn_chunks(int64_t HW) { return ceil_div(HW, SCN_CHUNK_PIX); }
 
 template <typename T>
 __global__ __launch_bounds__(256) void scenario_pack_kernel(const uint8_t* __restrict__ dw_t1, const float* __restrict__ rgb,
@@ -83,7 +80,9 @@ __global__ __launch_bounds__(256) void scenario_pack_kernel(const uint8_t* __res
   }
 }
 
-__device__ __forceinline__ double scn_join(int v, double a, double b) { return v == 1 ? fmin(a, b) : v == 2 ? fmax(a, b) : a + b; }
+struct ScnJoin {
+  __device__ __forceinline__ double operator()(int v, double a, double b) const { return v == 1 ? fmin(a, b) : v == 2 ? fmax(a, b) : a + b; }
+};
 
 __global__ __launch_bounds__(256) void scenario_result_kernel(const float* __restrict__ out, const float* __restrict__ temp_orig,
                                                               const uint8_t* __restrict__ dw_t1, const uint8_t* __restrict__ dw_t2,
@@ -99,8 +98,8 @@ __global__ __launch_bounds__(256) void scenario_result_kernel(const float* __res
   float* tc = temp_c + (size_t)n * HW;
   float* dl = delta != nullptr ? delta + (size_t)n * HW : nullptr;
   const bool have = temp_orig != nullptr;
-  const int64_t q0 = (int64_t)blockIdx.x * SCN_CHUNK_PIX;
-  const int npx = (int)(HW - q0 < SCN_CHUNK_PIX ? HW - q0 : SCN_CHUNK_PIX);
+  const int64_t q0 = (int64_t)blockIdx.x * CHUNK_PIX;
+  const int npx = (int)(HW - q0 < CHUNK_PIX ? HW - q0 : CHUNK_PIX);
 
   double acc[SCN_NV] = {0.0, INFINITY, -INFINITY, 0.0, 0.0};
   for (int idx = threadIdx.x; idx < npx; idx += 256) {
@@ -123,34 +122,12 @@ __global__ __launch_bounds__(256) void scenario_result_kernel(const float* __res
     }
   }
 
-  // lanes of a wave: xor butterfly (addition, fmin and fmax commute: every lane ends with the same bits)
-#pragma unroll
-  for (int v = 0; v < SCN_NV; ++v) {
-#pragma unroll
-    for (int s = 32; s >= 1; s >>= 1) acc[v] = scn_join(v, acc[v], __shfl_xor(acc[v], s, 64));
-  }
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  if (lane == 0) {
-#pragma unroll
-    for (int v = 0; v < SCN_NV; ++v) wsum[wave][v] = acc[v];
-  }
-  __syncthreads();
   double* prow = part + (size_t)blockIdx.y * chunks * SCN_NV;
-  if (threadIdx.x < SCN_NV) {
-    const int v = threadIdx.x;
-    double s = wsum[0][v];
-    for (int w = 1; w < 4; ++w) s = scn_join(v, s, wsum[w][v]);
-    prow[(size_t)blockIdx.x * SCN_NV + v] = s;
-  }
+  block_join<SCN_NV>(acc, wsum, ScnJoin(), prow + (size_t)blockIdx.x * SCN_NV);
   if (!last_block_of(tickets + blockIdx.y, (unsigned)chunks)) return;
 
   // level 2: the scenario's chunk partials in chunk order, then the finished row
-  if (threadIdx.x < SCN_NV) {
-    const int v = threadIdx.x;
-    double s = prow[v];
-    for (int c = 1; c < chunks; ++c) s = scn_join(v, s, prow[(size_t)c * SCN_NV + v]);
-    wsum[0][v] = s;
-  }
+  if (threadIdx.x < SCN_NV) wsum[0][threadIdx.x] = chunk_join(prow, chunks, SCN_NV, threadIdx.x, ScnJoin());
   __syncthreads();
   if (threadIdx.x < SCN_ROW) {
     const int e = threadIdx.x;
@@ -175,13 +152,11 @@ int mau_scenario_max_classes(void) { return SCN_MAX_CLS; }
 
 int mau_scenario_result_row_elems(void) { return SCN_ROW; }
 
-int mau_scenario_result_chunks(int H, int W) { return H > 0 && W > 0 ? scn_chunks((int64_t)H * W) : 0; }
+int mau_scenario_result_chunks(int H, int W) { return H > 0 && W > 0 ? chunks_of((int64_t)H * W) : 0; }
 
 size_t mau_scenario_result_ws_elems(int N, int H, int W) {
   if (N <= 0 || H <= 0 || W <= 0) return 0;
-  // the launches of one call reuse the partials of the first mau_reduce_tickets_elems() scenarios
-  const int per = mau_reduce_tickets_elems();
-  return (size_t)(N < per ? N : per) * scn_chunks((int64_t)H * W) * SCN_NV;
+  return (size_t)ticket_ws_rows(N) * chunks_of((int64_t)H * W) * SCN_NV;
 }
 
 int mau_scenario_pack(const unsigned char* dw_t1, const float* rgb, const float* ndvi, const float* temp, const unsigned char* canvas,
@@ -208,17 +183,11 @@ int mau_scenario_result(const float* out, const float* temp_orig, const unsigned
   MAU_REQUIRE(N > 0 && H > 0 && W > 0, "scenario_result: non-positive dimension (N %d, H %d, W %d)", N, H, W);
   MAU_REQUIRE((int64_t)H * W <= (1 << 30), "scenario_result: maps of at most 2^30 pixels");
   const int64_t HW = (int64_t)H * W;
-  const int chunks = scn_chunks(HW);
-  // one ticket per scenario: mau_reduce_tickets_elems() scenarios per launch
-  const int per = mau_reduce_tickets_elems();
-  for (int n0 = 0; n0 < N; n0 += per) {
-    const int nn = N - n0 < per ? N - n0 : per;
+  const int chunks = chunks_of(HW);
+  return for_ticket_rows(N, "scenario_result_kernel", [&](int n0, int nn) {
     MAU_LAUNCH(scenario_result_kernel, dim3(chunks, nn), dim3(256), 0, (hipStream_t)stream, out, temp_orig, dw_t1, dw_t2, (float)temp_std,
                (float)temp_mean, ndvi, temp_c, delta, ws, tickets, rows, HW, n0);
-    const int st = check_launch("scenario_result_kernel");
-    if (st != 0) return st;
-  }
-  return 0;
+  });
 }
 
 }  // extern "C"

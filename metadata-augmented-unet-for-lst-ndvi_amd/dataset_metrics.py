@@ -44,7 +44,13 @@ P_N, P_MEAN, P_M2, P_MIN, P_MAX, P_L1, P_NAN, P_BAD = range(PLANE_ROW)
 PLANE_NDVI_DIFF, PLANE_TEMP_DIFF = 7, 8
 N_PLANES = 9
 ROW = PLANES0 + N_PLANES * PLANE_ROW
-CHUNK_PIX = 4096
+
+
+def __getattr__(name):
+    if name == "CHUNK_PIX":                             # the library's chunk (csrc/chunk_reduce.h): a power of two
+        from ._lib import lib
+        return (1 << 30) // lib.mau_plane_moments_chunks(1 << 30)
+    raise AttributeError(f"module {__name__!r} has no attribute {name!r}")
 
 
 def _columns() -> List[str]:
@@ -226,21 +232,6 @@ def tile_metrics_host(sample_arrays: Mapping, metrics: Mapping) -> dict:
 # --------------------------------------------------------------------------- #
 # the kernel
 # --------------------------------------------------------------------------- #
-def _check(t, what: str, name: str, dtype, shape_doc: str, ndim: int):
-    import torch
-    from . import functional as F_
-    if not isinstance(t, torch.Tensor):
-        raise TypeError(f"{what}: {name} must be a torch.Tensor, got {type(t).__name__}")
-    F_._require_cuda(t, what)
-    if t.dtype != dtype:
-        raise TypeError(f"{what}: {name} must be {dtype}, got {t.dtype}")
-    if t.dim() != ndim or t.numel() == 0:
-        raise ValueError(f"{what}: {name} must be a non-empty {shape_doc}, got {tuple(t.shape)}")
-    t = t.detach().contiguous()
-    # 16-byte aligned bases: the kernel's load width, and with it the order of its sums, is then a function of H * W alone
-    return t if t.data_ptr() % 16 == 0 else t.clone(memory_format=torch.contiguous_format)
-
-
 def tile_stats(cls_a, cls_b, cont, targets):
     """(B,H,W) uint8 x 2, (B,5,H,W) fp32, (B,2,H,W) fp32 on the device -> (B, R) fp64 device tensor (the row of ``mau_tile_stats``,
     include/mau_hip.h), one launch per 64 samples, no synchronisation.  A row depends on its own sample only: not on B, not on
@@ -248,10 +239,10 @@ def tile_stats(cls_a, cls_b, cont, targets):
     import torch
     from . import functional as F_
     from .functional import call, lib
-    a = _check(cls_a, "tile_stats", "cls_a", torch.uint8, "(B, H, W)", 3)
-    b = _check(cls_b, "tile_stats", "cls_b", torch.uint8, "(B, H, W)", 3)
-    c = _check(cont, "tile_stats", "cont", torch.float32, "(B, 5, H, W)", 4)
-    t = _check(targets, "tile_stats", "targets", torch.float32, "(B, 2, H, W)", 4)
+    a = F_._device_planes(cls_a, "tile_stats", "cls_a", torch.uint8, 3, "(B, H, W)")
+    b = F_._device_planes(cls_b, "tile_stats", "cls_b", torch.uint8, 3, "(B, H, W)")
+    c = F_._device_planes(cont, "tile_stats", "cont", torch.float32, 4, "(B, 5, H, W)")
+    t = F_._device_planes(targets, "tile_stats", "targets", torch.float32, 4, "(B, 2, H, W)")
     B, H, W = a.shape
     if b.shape != a.shape or c.shape != (B, N_CONT, H, W) or t.shape != (B, N_TGT, H, W):
         raise ValueError(f"tile_stats: cls_a {tuple(a.shape)}, cls_b {tuple(b.shape)}, cont {tuple(c.shape)}, targets {tuple(t.shape)}: "

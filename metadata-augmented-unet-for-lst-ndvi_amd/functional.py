@@ -51,6 +51,21 @@ def _require_cuda(t: torch.Tensor, what: str):
             "fallback. Move the module and its inputs to a 'cuda' (ROCm) device.")
 
 
+def _device_planes(t, what: str, name: str, dtype, ndim: int, shape_doc: str) -> torch.Tensor:
+    """The argument check of the analysis entry points that read whole planes (``mau_plane_moments``, ``mau_tile_stats``): a
+    non-empty device tensor of ``dtype`` and rank ``ndim``, returned detached, contiguous and on a 16-byte aligned base -- the
+    kernels' load width, and with it the order of their sums, is then a function of H * W alone."""
+    if not isinstance(t, torch.Tensor):
+        raise TypeError(f"{what}: {name} must be a torch.Tensor, got {type(t).__name__}")
+    _require_cuda(t, what)
+    if t.dtype != dtype:
+        raise TypeError(f"{what}: {name} must be {dtype}, got {t.dtype}")
+    if t.dim() != ndim or t.numel() == 0:
+        raise ValueError(f"{what}: {name} must be a non-empty {shape_doc}, got {tuple(t.shape)}")
+    t = t.detach().contiguous()
+    return t if t.data_ptr() % 16 == 0 else t.clone(memory_format=torch.contiguous_format)
+
+
 def _ld(t: torch.Tensor) -> int:
     """Pixel stride (elements) of an NHWC-ld tensor or channel-sliced view of one."""
     n, h, w, _ = t.shape

@@ -86,25 +86,16 @@ def bin_stats_host(coords, planes, centers):
 # --------------------------------------------------------------------------- #
 # the kernels
 # --------------------------------------------------------------------------- #
-def _check_targets(targets: torch.Tensor, what: str) -> torch.Tensor:
-    F_._require_cuda(targets, what)
-    if targets.dtype != torch.float32:
-        raise TypeError(f"{what}: targets must be float32, got {targets.dtype}")
-    if targets.dim() != 4 or targets.numel() == 0:
-        raise ValueError(f"{what}: targets must be a non-empty (B, C, H, W), got {tuple(targets.shape)}")
-    t = targets.detach().contiguous()
-    # a 16-byte aligned base: the kernel's load width, and with it the order of its sums, is then a function of H * W alone
-    return t if t.data_ptr() % 16 == 0 else t.clone(memory_format=torch.contiguous_format)
-
-
-def plane_moments(targets: torch.Tensor) -> torch.Tensor:
+def plane_moments(targets: torch.Tensor, ws: Optional[torch.Tensor] = None) -> torch.Tensor:
     """(B, C, H, W) fp32 on the device -> (B, C, 4) fp64 device tensor of (n, mean, M2, non-finite count) per plane, one launch per
-    64 planes.  A row depends on its own plane only: not on B, not on the plane's position; repeated calls agree bit for bit."""
-    t = _check_targets(targets, "plane_moments")
+    64 planes.  A row depends on its own plane only: not on B, not on the plane's position; repeated calls agree bit for bit.
+    ws: an fp64 device workspace of at least ``mau_plane_moments_ws_elems(B, C, H * W)`` elements (None: allocated here)."""
+    t = F_._device_planes(targets, "plane_moments", "targets", torch.float32, 4, "(B, C, H, W)")
     B, C, H, W = t.shape
     dev = t.device
     rows = torch.empty((B, C, _ROW), dtype=torch.float64, device=dev)
-    ws = torch.empty(lib.mau_plane_moments_ws_elems(B, C, H * W), dtype=torch.float64, device=dev)
+    if ws is None:
+        ws = torch.empty(lib.mau_plane_moments_ws_elems(B, C, H * W), dtype=torch.float64, device=dev)
     call("mau_plane_moments", t.data_ptr(), rows.data_ptr(), ws.data_ptr(), F_._tickets(dev).data_ptr(), B, C, H * W, F_._stream())
     return rows
 
@@ -157,7 +148,7 @@ class BinStats:
     def update(self, targets: torch.Tensor, metadata: torch.Tensor) -> None:
         """Two launches on the current stream, no host synchronisation.  targets (B, channels, H, W) fp32, metadata (B, F) fp32 --
         normalised, as the dataset holds it -- both on the device."""
-        t = _check_targets(targets, "BinStats.update")
+        t = F_._device_planes(targets, "BinStats.update", "targets", torch.float32, 4, "(B, C, H, W)")
         F_._require_cuda(metadata, "BinStats.update")
         B, C, H, W = t.shape
         if C != self.channels:
@@ -176,9 +167,7 @@ class BinStats:
         need = lib.mau_plane_moments_ws_elems(B, C, H * W)
         if self._ws is None or self._ws.numel() < need:
             self._ws = torch.empty(need, dtype=torch.float64, device=self.device)
-        rows = torch.empty((B, C, _ROW), dtype=torch.float64, device=self.device)
-        call("mau_plane_moments", t.data_ptr(), rows.data_ptr(), self._ws.data_ptr(), F_._tickets(self.device).data_ptr(), B, C, H * W,
-             F_._stream())
+        rows = plane_moments(t, self._ws)
         call("mau_bin_moments", rows.data_ptr(), md.data_ptr(), md.stride(0), self._cols, self._std, self._mean, self._edges.data_ptr(),
              self.table.data_ptr(), B, C, len(self.axes), self.bins, F_._stream())
 
