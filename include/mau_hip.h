@@ -511,6 +511,42 @@ int mau_scenario_result(const float* out, const float* temp_orig, const unsigned
                         double temp_std, float* ndvi, float* temp_c, float* delta, double* rows, double* ws, unsigned* tickets, int N,
                         int H, int W, mau_stream_t stream);
 
+/* ---- model comparison: M heads' outputs of ONE tile against one target (the developer app's Model Comparison page,
+ *      app_dev/pages/1_Model_Comparison.py with app_dev/app_src/utils.py:170-271), ONE launch each.  Additive to ABI 5 ----
+ * mau_compare_result: out (M,2,H,W) fp32 NCHW, the M heads' outputs (channel 0 NDVI, channel 1 normalised temperature);
+ * tgt (2,H,W) fp32, the normalised target.
+ *   pred_u (M,2,H,W) fp32: channel 0 as it is; channel 1 = fl32(fl32(out * fl32(temp_std)) + fl32(temp_mean)), two separately
+ *                          rounded fp32 operations, never an FMA (utils.py:260-261; as mau_scenario_result);
+ *   gt_u (2,H,W) fp32    = the same rule on the target, written once;
+ *   err (M,2,H,W) fp32   = fl32(pred_u - gt_u);
+ *   rows (M * 2, mau_compare_row_elems() = 40) fp64, row m * 2 + c: five regions of eight entries, in the order whole tile,
+ *     top-left, top-right, bottom-left, bottom-right -- rows [0, H/2) | [H/2, H), columns [0, W/2) | [W/2, W), integer division
+ *     (utils.py:173-178).  Entries of a region:
+ *       [0] its pixel count  [1] gt min  [2] gt max  [3] pred min  [4] pred max  [5] max |err|  [6] sum |err|  [7] sum err^2.
+ *     fmin / fmax skip a NaN, the sums carry it.  A region without pixels: count 0, minima +inf, maxima -inf, [5..7] 0.  The
+ *     whole-tile entries are the join of the four quadrants' in that order: ((TL o TR) o BL) o BR.
+ * Sums are fp64 in a fixed order: a workgroup owns a run of pixels of ONE (model, channel) plane (mau_compare_chunks(H, W)
+ * workgroups per plane, a function of H * W alone), the workgroup that draws the plane's last ticket joins its partials in chunk
+ * order -- no float atomics; a row's bits do not depend on M or on the model's place, and repeat.  16-byte accesses when
+ * H * W % 4 == 0 and the five tensors are 16-byte aligned, 4-byte ones otherwise (the two forms add in different orders).
+ * ws: fp64 workspace of mau_compare_ws_elems(M, H, W) elements; tickets: a ZEROED mau_reduce_tickets_elems() buffer (left zeroed;
+ * see mau_reduce_rows_f64).  One launch per mau_reduce_tickets_elems() rows. */
+int mau_compare_row_elems(void);
+int mau_compare_chunks(int H, int W);
+size_t mau_compare_ws_elems(int M, int H, int W);
+int mau_compare_result(const float* out, const float* tgt, double temp_mean, double temp_std, float* pred_u, float* gt_u, float* err,
+                       double* rows, double* ws, unsigned* tickets, int M, int H, int W, mau_stream_t stream);
+/* mau_compare_inputs: the page's views of one compact sample (utils.py:224-252).  cls_a, cls_b (H,W) uint8 class ids; cont (5,H,W)
+ * fp32, normalised rgb (3), ndvi, temperature; palette (ncls,3) uint8 RGB in class order, ncls in [1, mau_scenario_max_classes()];
+ * norm: 8 fp64 = rgb_mean[3], rgb_std[3], temp_mean, temp_std.
+ *   rgb8 (H,W,3) uint8   = clip(((double)x * rgb_std[c] + rgb_mean[c]) * 255.0, 0, 255) truncated toward zero: fp64, every operation
+ *                          rounded on its own (a float32 array times a float64 array, utils.py:225-226); a NaN gives 0;
+ *   temp_c (H,W) fp32    = the two-rounding fp32 rule above (utils.py:229);   ndvi (H,W) fp32 = the plane as it is;
+ *   dw_t1_rgb, dw_t2_rgb (H,W,3) uint8 = palette[cls_a], palette[cls_b]; a class id >= ncls gives (0,0,0). */
+int mau_compare_inputs(const unsigned char* cls_a, const unsigned char* cls_b, const float* cont, const unsigned char* palette,
+                       const double* norm, unsigned char* rgb8, float* temp_c, float* ndvi, unsigned char* dw_t1_rgb,
+                       unsigned char* dw_t2_rgb, int H, int W, int ncls, mau_stream_t stream);
+
 /* ---- ground-truth sensitivity (test/generate_ground_truth_sensitivity.py): binned mean / standard deviation of the targets of a
  *      split, TWO launches per batch, no target kept on the host.  Additive to ABI 5 ----
  * A moment row is mau_moments_row_elems() = 4 fp64: [0] n, the number of values  [1] their mean  [2] M2 = sum (x - mean)^2

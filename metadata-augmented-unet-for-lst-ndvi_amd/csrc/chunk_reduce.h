@@ -1,5 +1,5 @@
 // chunk_reduce.h -- the two-level fixed-order fp64 reduction of the analysis kernels (evalmetrics.hip, scenario.hip, gtstats.hip,
-// tilestats.hip, loss_terms.hip; the launch loop also head.hip's mau_head_mean), written once.
+// tilestats.hip, compare.hip, loss_terms.hip; the launch loop also head.hip's mau_head_mean), written once.
 //
 // A row (a plane, a scenario, a sample) is cut into chunks of CHUNK_PIX consecutive pixels, one 256-thread workgroup each -- the
 // chunking is a function of the row's size alone.  The order of every join is fixed:
