@@ -21,6 +21,8 @@
 //              throughput problem -- two gate rows per thread measured 23 % slower, packed FMAs (also hipcc's SLP-packed ones:
 //              built with -fno-slp-vectorize) slower than scalar.  In training the model runs it on a side stream.
 // Arithmetic is fp32 throughout; gate nonlinearities on the hardware exp / rcp.
+// Pinned by tests/test_gpu_temporal.py through the C ABI: every HP and CPT instantiation at H = 1 .. 128 around the class boundaries,
+// T = 1 .. 41 around the 8-step blocks, the dW_hh chunk seams at B*T = 512 .. 640, against the float64 loop of tests/temporal_ref.py.
 #include "mau_common.h"
 
 namespace mau {
@@ -159,7 +161,7 @@ __global__ __launch_bounds__(4 * HP) void lstm_bwd_kernel(const float* __restric
   constexpr int GP = HP + 8, OROW = 4 * GP;                         // gradient row: [gate][GP]; the pitch puts the four gates'
                                                                     // 16-byte reads of a lane group on distinct banks (with
                                                                     // pitch HP = 96 gates 0/2 and 1/3 collide: every read 2x)
-  constexpr int NLD = S * ROW / NT;                                 // staged values per thread and block (20)
+  constexpr int NLD = S * ROW / NT;                                 // staged values per thread and block (10)
   static_assert(S * ROW % NT == 0, "staging loop");
   extern __shared__ __attribute__((aligned(16))) float lsm[];
   float* inb = lsm;                                                 // [2][S][ROW]
