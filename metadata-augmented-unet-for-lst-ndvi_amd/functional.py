@@ -12,10 +12,10 @@ from __future__ import annotations
 
 import contextlib
 import dataclasses
-
 import os
+from collections import namedtuple
 from dataclasses import dataclass
-from typing import List, Optional, Sequence, Tuple
+from typing import List, Optional
 
 import torch
 
@@ -282,11 +282,7 @@ class ToNHWC(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, g):
-        g = _as_nhwc(g)
-        N, H, W, _ = g.shape
-        out = torch.empty((N, ctx.C, H, W), dtype=torch.float32, device=g.device)
-        call("mau_nhwc_to_nchw", g.data_ptr(), out.data_ptr(), dtype_code(g.dtype), N, ctx.C, H, W, _ld(g), _stream())
-        return out, None
+        return to_nchw(Act(g, ctx.C)), None
 
 
 def to_nchw(a: Act) -> torch.Tensor:
@@ -380,14 +376,426 @@ def _join_side_when_backward_ends(dev):
 _DGRAD_FIRST = None
 
 
-def _conv_fwd(x, x1, st, emb, emb_ws, E, wpk, bias, post, y, Cout, slab, code, N, H, W, stream):
-    """One launch of the implicit-GEMM convolution over cat([x, x1, broadcast(emb)], channels)."""
+# What every launch of one conv-bn-relu layer is given, built once per forward and once per backward (ldy = pad8(Cout): pixel stride of
+# the conv output and of the activation; code / act_dt: the activations' MAU_* code and torch dtype), and the layer's saved tensors
+_Geom = namedtuple("_Geom", "N H W Cin Cout ldy code act_dt dev stream")
+_Saved = namedtuple("_Saved", "x x1 emb weight y scale shift mean invstd a w2 out argidx")
+
+
+def _ptr(t):
+    return None if t is None else t.data_ptr()
+
+
+# ---- launches shared by ConvBNReLU and the stand-alone operators below ----
+def _pool_fwd(x, C, stream):
+    """nn.MaxPool2d(2, 2) of an NHWC-ld tensor."""
+    N, H, W, _ = x.shape
+    ldy = pad8(C)
+    y = torch.empty((N, H // 2, W // 2, ldy), dtype=x.dtype, device=x.device)
+    call("mau_maxpool2x2_fwd", x.data_ptr(), _ld(x), y.data_ptr(), ldy, dtype_code(x.dtype), N, H, W, C, stream)
+    return y
+
+
+def _pool_bwd(x, C, dy, dskip, stream):
+    """Gradient of maxpool2x2 w.r.t. its materialised input ``x``, plus ``dskip`` (the skip connection's gradient of ``x``) in the same pass."""
+    dy = _as_nhwc(dy)
+    N, H, W, _ = x.shape
+    dx = torch.empty((N, H, W, pad8(C)), dtype=x.dtype, device=x.device)
+    tail = (dx.data_ptr(), pad8(C), dtype_code(x.dtype), N, H, W, C, stream)
+    if dskip is None:
+        call("mau_maxpool2x2_bwd", x.data_ptr(), _ld(x), dy.data_ptr(), _ld(dy), *tail)
+    else:
+        dskip = _as_nhwc(dskip)
+        call("mau_maxpool2x2_bwd_add", x.data_ptr(), _ld(x), dy.data_ptr(), _ld(dy), dskip.data_ptr(), _ld(dskip), *tail)
+    return dx
+
+
+def _resize_fwd(src, C, size, stream, dst=None, choff=0):
+    """Bilinear (align_corners=True) resize to ``size = (H, W)``: a fresh tensor, or channels [choff, choff + C) of ``dst`` (choff % 8 == 0)."""
+    N, h, w, _ = src.shape
+    H, W = size
+    if dst is None:
+        dst = torch.empty((N, H, W, pad8(C)), dtype=src.dtype, device=src.device)
+    call("mau_resize_bilinear_fwd", src.data_ptr(), _ld(src), h, w, dst.data_ptr(), _ld(dst), choff, dtype_code(src.dtype), N, H, W, C, stream)
+    return dst
+
+
+def _resize_bwd(g, goff, C, size, stream):
+    """Adjoint of ``_resize_fwd``: channels [goff, goff + C) of the gradient ``g`` -> the gradient of the ``size = (h, w)`` source."""
+    N, H, W, _ = g.shape
+    h, w = size
+    d = torch.empty((N, h, w, pad8(C)), dtype=g.dtype, device=g.device)
+    call("mau_resize_bilinear_bwd", g.data_ptr(), _ld(g), goff, H, W, d.data_ptr(), pad8(C), dtype_code(g.dtype), N, h, w, C, stream)
+    return d
+
+
+def _head_fwd(a, C, w2, hb, tanh0, stream):
+    """Final 1x1 conv (+ tanh on channel 0) of a materialised activation -> (N, Co, H, W) fp32."""
+    N, H, W, _ = a.shape
+    Co = w2.shape[0]
+    out = torch.empty((N, Co, H, W), dtype=torch.float32, device=a.device)
+    call("mau_head_fwd", a.data_ptr(), _ld(a), w2.data_ptr(), hb.data_ptr(), out.data_ptr(), tanh0, dtype_code(a.dtype), N, H * W, C, Co, stream)
+    return out
+
+
+def _head_slab(N, HW, C, Co, dev):
+    """Per-row partial sums of the head's dW and db (the 7 unwritten columns per output channel are never read back)."""
+    return torch.empty((lib.mau_head_bwd_rows(N, HW), lib.mau_head_bwd_rowlen(C, Co)), dtype=torch.float32, device=dev)
+
+
+def _head_param_grads(hslab, C, Co, wshape, stream):
+    """Head slab -> (dW, db), one launch."""
+    hrows, rowlen = hslab.shape
+    red = torch.empty(rowlen, dtype=torch.float32, device=hslab.device)
+    ws = torch.empty(lib.mau_reduce_rows_ws_elems(hrows, rowlen), dtype=torch.float64, device=hslab.device)
+    call("mau_reduce_rows_f32", hslab.data_ptr(), hrows, rowlen, rowlen, red.data_ptr(), ws.data_ptr(),
+         _tickets(hslab.device).data_ptr() if _FUSED_REDUCE else None, stream)
+    red = red.view(Co, pad8(C) + 8)
+    return red[:, :C].reshape(wshape).contiguous(), red[:, pad8(C)].contiguous()
+
+
+def _head_bwd(a, C, w2, out, dout, tanh0, wshape, stream):
+    """Backward of the head on a materialised activation -> (da, dW, db)."""
+    N, H, W, _ = a.shape
+    Co = w2.shape[0]
+    dout = dout.contiguous().float()
+    da = torch.empty((N, H, W, pad8(C)), dtype=a.dtype, device=a.device)
+    hslab = _head_slab(N, H * W, C, Co, a.device)
+    call("mau_head_bwd", a.data_ptr(), _ld(a), w2.data_ptr(), out.data_ptr(), dout.data_ptr(), da.data_ptr(), pad8(C), hslab.data_ptr(), tanh0,
+         dtype_code(a.dtype), N, H * W, C, Co, stream)
+    return (da, *_head_param_grads(hslab, C, Co, wshape, stream))
+
+
+# ---- ConvBNReLU.forward, stage by stage ----
+def _conv_launch(g: _Geom, st: BNState, src, w, bias, post, y, slab=None, x8=None):
+    """One launch of the layer's convolution over ``src = (x, x1, emb, emb_ws)`` into ``y``.  ``post = (scale, shift)``: that affine map
+    + ReLU in the epilogue; ``slab``: receives the per-tile BatchNorm sums.  ``st.first``: conv0_0.conv1 straight from the fp32 NCHW
+    input and the fp32 master weights ``w`` (no layout kernel, no weight pack), ``x8`` = the input in the activation type as NHWC-8, a
+    by-product of the same pass; otherwise the implicit-GEMM convolution over cat([x, x1, broadcast(emb)], channels), ``w`` = its pack."""
+    x, x1, emb, emb_ws = src
     scale, shift = post if post is not None else (None, None)
-    call("mau_conv3x3_fwd2", x.data_ptr(), _ld(x), st.C0, x1.data_ptr() if x1 is not None else None,
-         _ld(x1) if x1 is not None else 0, st.C1 if x1 is not None else 0, emb.data_ptr() if E else None,
-         emb_ws.data_ptr() if E else None, E, wpk.data_ptr(), bias.data_ptr() if bias is not None else None,
-         scale.data_ptr() if scale is not None else None, shift.data_ptr() if shift is not None else None,
-         y.data_ptr(), _ld(y), Cout, slab.data_ptr() if slab is not None else None, code, N, H, W, stream)
+    if st.first:
+        call("mau_conv3x3_first_fwd", x.data_ptr(), st.C0, w.data_ptr(), _ptr(bias), _ptr(scale), _ptr(shift), y.data_ptr(), _ld(y),
+             g.Cout, _ptr(slab), _ptr(x8), g.code, g.N, g.H, g.W, g.stream)
+        return
+    E = 0 if emb is None else emb.shape[1]
+    call("mau_conv3x3_fwd2", x.data_ptr(), _ld(x), st.C0, _ptr(x1), _ld(x1) if x1 is not None else 0, st.C1 if x1 is not None else 0,
+         emb.data_ptr() if E else None, emb_ws.data_ptr() if E else None, E, w.data_ptr(), _ptr(bias), _ptr(scale), _ptr(shift),
+         y.data_ptr(), _ld(y), g.Cout, _ptr(slab), g.code, g.N, g.H, g.W, g.stream)
+
+
+def _conv_inputs(x, x1, emb, weight, hw, st: BNState):
+    """Argument checks.  Returns the geometry, the loader sources (x, x1, emb, emb_ws) as the kernels take them, and the head as
+    (Co, tanh0, weight as (Co, Cout) fp32) or None."""
+    _require_cuda(x, "conv3x3")
+    if st.first:
+        # the network's first convolution on the input tensor as delivered (src/model.py:222, src/dataset.py:99-106)
+        if x1 is not None or emb is not None or x.dim() != 4 or x.shape[1] != st.C0 or st.C0 > lib.mau_conv3x3_first_max_channels():
+            raise RuntimeError("conv3x3 (first layer): expects one (N, C <= 8, H, W) fp32 input")
+        x = x.contiguous().float()
+        N, _, H, W = x.shape
+        act_dt = st.dtype
+    else:
+        x = _as_nhwc(x)
+        if x1 is not None:
+            x1 = _as_nhwc(x1)
+        N, H, W, _ = x.shape
+        act_dt = x.dtype
+    Cout, Cin = weight.shape[0], weight.shape[1]
+    g = _Geom(N, H, W, Cin, Cout, pad8(Cout), dtype_code(act_dt), act_dt, x.device, _stream())
+    E = 0 if emb is None else emb.shape[1]
+    C1 = st.C1 if x1 is not None else 0
+    if st.C0 + C1 + E != Cin:
+        raise RuntimeError(f"conv3x3: input has {st.C0}+{C1}+{E} channels, weight expects {Cin}")
+    if emb is not None:
+        emb = emb.contiguous().float()
+    dst = st.out_view                               # where the activation goes: a slot of a row buffer, or a fresh tensor
+    if dst is not None and (tuple(dst.shape) != (N, H, W, g.ldy) or dst.dtype != act_dt or Cout % 64 != 0):
+        raise RuntimeError("conv3x3: out_view must be an (N,H,W,Cout) NHWC-ld view of the activation dtype with Cout % 64 == 0")
+    if sum((st.pool, st.head is not None, st.up_to is not None)) > 1 or ((st.head is not None or st.up_to is not None) and dst is not None):
+        raise RuntimeError("conv3x3: pool / head / up_to are exclusive, and head / up_to write no activation (no out_view)")
+    head = None
+    if st.head is not None:
+        Co = hw.shape[0]
+        head = (Co, 1 if (Co == 2 and st.head) else 0, hw.detach().reshape(Co, Cout).contiguous().float())
+    emb_ws = torch.empty((N, E), dtype=act_dt, device=g.dev) if E else None
+    return g, (x, x1, emb, emb_ws), head
+
+
+def _conv_inference(g: _Geom, st: BNState, src, weight, bias, bn, head, hb):
+    """Eval-mode BN + ReLU are a fixed per-channel affine map -> folded into the conv epilogue.  In a frozen session
+    (UrbanPredictor.freeze_inference) the packed weights and the folded coefficients are computed once.  Returns the outputs."""
+    gamma, beta, rmean, rvar = bn[:4]
+    x, x1, emb, _ = src
+    y = st.out_view if st.out_view is not None else torch.empty((g.N, g.H, g.W, g.ldy), dtype=g.act_dt, device=g.dev)
+    fz = st.frozen if st.frozen is not None else {}
+    fkey = (_GENERATION[0], weight._version, gamma._version, rmean._version, rvar._version)
+    if "wf" not in fz or fz["wf"].dtype != g.act_dt or fz.get("key") != fkey:
+        # (an optimizer step -- of ANY model: the generation counter is global --, mark_params_updated() or an in-place
+        #  write re-derives the copies.)  Everything is refreshed IN PLACE: the packs are persistent buffers and
+        # scale / shift are allocated once per session, so a live GraphedInference graph, which holds these
+        # addresses, replays with the new values instead of reading freed memory.
+        fz["key"] = fkey
+        fz["wf"] = weight if st.first else pack_conv_weights(weight, g.code, forward=True, dgrad=False)[0]     # (first layer: the master weights themselves)
+        if "scale" not in fz or fz["scale"].device != g.dev or fz["scale"].numel() != g.Cout:
+            fz["scale"], fz["shift"] = (torch.empty(g.Cout, dtype=torch.float32, device=g.dev) for _ in range(2))
+        call("mau_bn_coeffs_eval", gamma.data_ptr(), beta.data_ptr(), rmean.data_ptr(), rvar.data_ptr(), st.eps, fz["scale"].data_ptr(),
+             fz["shift"].data_ptr(), None, None, g.Cout, g.stream)
+    pl = None
+    if st.pool and not st.first and _INFER_POOL_FUSED and x1 is None and (emb is None or not emb.shape[1]) and g.H >= 2 and g.W >= 2:
+        # an encoder block's second convolution: the pooled tensor comes out of the same launch (the 16x16x32 tilings take the
+        # 2x2 maxima from the registers they store; other tilings run the pooling kernel behind the convolution inside the call)
+        pl = torch.empty((g.N, g.H // 2, g.W // 2, g.ldy), dtype=g.act_dt, device=g.dev)
+        call("mau_conv3x3_fwd_pool", x.data_ptr(), _ld(x), st.C0, fz["wf"].data_ptr(), _ptr(bias), fz["scale"].data_ptr(),
+             fz["shift"].data_ptr(), y.data_ptr(), _ld(y), g.Cout, pl.data_ptr(), g.ldy, g.code, g.N, g.H, g.W, g.stream)
+    else:
+        _conv_launch(g, st, src, fz["wf"], bias, (fz["scale"], fz["shift"]), y)
+    if head is not None:
+        return (_head_fwd(y, g.Cout, head[2], hb, head[1], g.stream),)
+    if st.up_to is not None:
+        return (_resize_fwd(y, g.Cout, st.up_to, g.stream),)
+    if st.pool:
+        return y, (pl if pl is not None else _pool_fwd(y, g.Cout, g.stream))
+    return (y,)
+
+
+def _conv_with_stats(g: _Geom, st: BNState, src, w, bias, bn, x8):
+    """The convolution and the BatchNorm coefficients of its output: batch statistics (local: one launch; SyncBN: one all-reduce
+    per layer) with the running-statistics update, or the eval coefficients.  Returns y, (scale, shift, mean, invstd)."""
+    gamma, beta, rmean, rvar, nbt = bn
+    Cout, dev, stream = g.Cout, g.dev, g.stream
+    y = torch.empty((g.N, g.H, g.W, g.ldy), dtype=g.act_dt, device=dev)
+    coef = tuple(torch.empty(Cout, dtype=torch.float32, device=dev) for _ in range(4))
+    cptrs = tuple(t.data_ptr() for t in coef)
+    if not st.training:
+        call("mau_bn_coeffs_eval", gamma.data_ptr(), beta.data_ptr(), rmean.data_ptr(), rvar.data_ptr(), st.eps, *cptrs, Cout, stream)
+        _conv_launch(g, st, src, w, bias, None, y, None, x8)
+        return y, coef
+    npix = g.N * g.H * g.W
+    tiles = lib.mau_conv3x3_first_rows(g.N, g.H, g.W) if st.first else lib.mau_conv3x3_num_pixel_tiles(g.code, g.N, g.H, g.W, Cout)
+    slab = torch.empty((tiles, 2 * ((Cout + 63) // 64 * 64)), dtype=torch.float32, device=dev)
+    _conv_launch(g, st, src, w, bias, None, y, slab, x8)
+    if st.group is None:
+        # single GPU: slab -> fp64 partials -> second level + finalize by the last workgroup, ONE launch
+        ws = torch.empty(lib.mau_bn_stats_ws_elems(tiles, Cout), dtype=torch.float64, device=dev)
+        call("mau_bn_stats_finalize_train", slab.data_ptr(), tiles, float(npix), gamma.data_ptr(), beta.data_ptr(),
+             rmean.data_ptr(), rvar.data_ptr(), _ptr(nbt), st.momentum, st.eps, *cptrs, ws.data_ptr(),
+             _tickets(dev).data_ptr() if _FUSED_REDUCE else None, Cout, stream)
+    else:
+        # SyncBN: ONE collective per layer carries [sum(y) | sum(y^2) | local pixel count]; the count is summed
+        # with the statistics, so ranks with different local batch sizes still agree on the global moments
+        sums = torch.empty(2 * Cout + 1, dtype=torch.float64, device=dev)
+        ws = torch.empty(lib.mau_reduce_rows_ws_elems(tiles, 2 * Cout), dtype=torch.float64, device=dev)
+        call("mau_bn_stats_sums_f64", slab.data_ptr(), tiles, Cout, sums.data_ptr(), ws.data_ptr(), _tickets(dev).data_ptr(), float(npix), stream)
+        _all_reduce_(sums, st)
+        call("mau_bn_finalize_train", sums.data_ptr(), 0.0, gamma.data_ptr(), beta.data_ptr(), rmean.data_ptr(), rvar.data_ptr(), _ptr(nbt),
+             st.momentum, st.eps, *cptrs, Cout, stream)
+    return y, coef
+
+
+def _conv_activation(g: _Geom, st: BNState, y, scale, shift, head, hb):
+    """The activation stage: the fused head or upsample (no activation tensor), or BatchNorm + ReLU (+ pool) followed by the plain
+    head / upsample.  Returns (the layer's outputs, (activation, head output, pool arg-max bits) as far as the backward reads
+    them, whether the head / upsample ran fused)."""
+    N, H, W, Cout, ldy, stream = g.N, g.H, g.W, g.Cout, g.ldy, g.stream
+    fused = _FUSED_BN
+    if head is not None and fused and Cout <= lib.mau_head_bn_max_channels() and H * W >= 32:
+        # the head reads y and applies BatchNorm + ReLU on the fly: no activation tensor
+        Co, tanh0, w2 = head
+        out = torch.empty((N, Co, H, W), dtype=torch.float32, device=g.dev)
+        call("mau_head_bn_fwd", y.data_ptr(), ldy, scale.data_ptr(), shift.data_ptr(), w2.data_ptr(), hb.data_ptr(), out.data_ptr(), tanh0,
+             g.code, N, H * W, Cout, Co, stream)
+        return (out,), (None, out, None), True
+    if st.up_to is not None and fused and _FUSED_UP and H <= st.up_to[0] and W <= st.up_to[1]:
+        # the resize applies BatchNorm + ReLU to the corners it loads
+        Hu, Wu = st.up_to
+        up = torch.empty((N, Hu, Wu, ldy), dtype=g.act_dt, device=g.dev)
+        call("mau_resize_bilinear_bn_fwd", y.data_ptr(), ldy, H, W, scale.data_ptr(), shift.data_ptr(), up.data_ptr(), ldy, 0, g.code,
+             N, Hu, Wu, Cout, stream)
+        return (up,), (None, None, None), True
+    a = st.out_view if st.out_view is not None else torch.empty_like(y)
+    if st.pool and H >= 2 and W >= 2:
+        pl = torch.empty((N, H // 2, W // 2, ldy), dtype=g.act_dt, device=g.dev)
+        # 2 bits per (window, channel): which pixel holds the maximum -- the routing of the pool's backward (fused with the
+        # BatchNorm backward passes, no activation is re-read for it)
+        argidx = torch.empty((N, H // 2, W // 2, ldy // 8), dtype=torch.int16, device=g.dev) if fused else None
+        call("mau_bn_relu_apply_pool", y.data_ptr(), ldy, scale.data_ptr(), shift.data_ptr(), a.data_ptr(), _ld(a),
+             pl.data_ptr(), ldy, _ptr(argidx), g.code, N, H, W, Cout, stream)
+        # (the activation is saved only where the backward still reads it: the unfused pool's arg-max, the unfused head's dW)
+        return (a, pl), (None if fused else a, None, argidx), False
+    call("mau_bn_relu_apply", y.data_ptr(), ldy, scale.data_ptr(), shift.data_ptr(), a.data_ptr(), _ld(a), g.code, N * H * W, Cout, stream)
+    if head is not None:
+        out = _head_fwd(a, Cout, head[2], hb, head[1], stream)
+        return (out,), (a, out, None), False
+    if st.up_to is not None:
+        return (_resize_fwd(a, Cout, st.up_to, stream),), (None, None, None), False
+    return ((a, None) if st.pool else (a,)), (None, None, None), False
+
+
+def _conv_save(ctx, st: BNState, src, weight, wd, y, coef, head, hw, outs, kept, fused):
+    """What the backward needs."""
+    # (the context must not hold the output: st.out_view IS the returned activation, and node -> ctx -> st -> out_view -> grad_fn
+    #  -> node is a reference cycle that only Python's cycle collector frees -- a whole step's graph, its AccumulateGrad nodes
+    #  included, then outlives the step; a hipGraph capture that meets those stale nodes dies in hipStreamEndCapture)
+    ctx.st = st if st.out_view is None else dataclasses.replace(st, out_view=None)
+    x, x1, emb, _ = src
+    ctx.wd = wd                           # data-gradient pack of THIS forward's weights
+    ctx.pooled = len(outs) == 2 and outs[1] is not None
+    ctx.head = (head[0], head[1], tuple(hw.shape), fused) if head is not None else None
+    ctx.up = (st.up_to, fused) if st.up_to is not None else None
+    a, out, argidx = kept
+    ctx.save_for_backward(*_Saved(x, x1, emb, weight, y, *coef, a, head[2] if head is not None else None, out, argidx))
+
+
+# ---- ConvBNReLU.backward, stage by stage.  A dz stage is (g, st, ctx, sv, da, dpl) -> (dy, g32, dhw, dhb): its reduce kernel, the
+# ---- shared _finish_sums, its apply kernel; g32 = [dbeta | dgamma], the LOCAL sums, rounded to fp32 by the reducer
+def _dz_begin(g: _Geom, sv):
+    """(slab of the reduce pass, dy, the pointers of scale / shift / mean / invstd)"""
+    slab = torch.empty((lib.mau_bn_bwd_rows(g.N * g.H * g.W), 2 * g.Cout), dtype=torch.float32, device=g.dev)
+    return slab, torch.empty_like(sv.y), (sv.scale.data_ptr(), sv.shift.data_ptr(), sv.mean.data_ptr(), sv.invstd.data_ptr())
+
+
+def _finish_sums(g: _Geom, st: BNState, slab):
+    """slab -> sums (fp64) + g32 (fp32), one launch; data parallel: all-reduce with the pixel count appended.
+    Returns (sums for the apply pass, count argument, g32)."""
+    rows, C2 = slab.shape
+    npix = g.N * g.H * g.W
+    sync = st.training and st.group is not None
+    sums = torch.empty(C2 + 1, dtype=torch.float64, device=g.dev)
+    g32 = torch.empty(C2, dtype=torch.float32, device=g.dev)
+    ws = torch.empty(lib.mau_reduce_rows_ws_elems(rows, C2), dtype=torch.float64, device=g.dev)
+    call("mau_reduce_rows_f64_f32", slab.data_ptr(), rows, C2, C2, sums.data_ptr(), g32.data_ptr(), ws.data_ptr(),
+         _tickets(g.dev).data_ptr() if (_FUSED_REDUCE or sync) else None, float(npix) if sync else 0.0, g.stream)
+    if not st.training:
+        return torch.zeros_like(sums), float(npix), g32      # eval-mode BN is a fixed affine map
+    if sync:                                                 # the global count travels with the sums (see forward)
+        _all_reduce_(sums, st)
+        return sums, 0.0, g32
+    return sums, float(npix), g32
+
+
+def _dz_fused_head(g: _Geom, st: BNState, ctx, sv, da, dpl):
+    """Head + BatchNorm backward, two passes over y: da = W_head^T dz is recomputed from dout in both."""
+    Co, tanh0, hshape, _ = ctx.head
+    slab, dy, cptrs = _dz_begin(g, sv)
+    dout = da.contiguous().float()
+    hslab = _head_slab(g.N, g.H * g.W, g.Cout, Co, g.dev)
+    call("mau_head_bn_bwd_reduce", sv.y.data_ptr(), g.ldy, *cptrs, sv.w2.data_ptr(), sv.out.data_ptr(), dout.data_ptr(), slab.data_ptr(),
+         g.Cout, hslab.data_ptr(), tanh0, g.code, g.N, g.H * g.W, g.Cout, Co, g.stream)
+    sums, count, g32 = _finish_sums(g, st, slab)
+    dhw, dhb = _head_param_grads(hslab, g.Cout, Co, hshape, g.stream)
+    call("mau_head_bn_bwd_apply", sv.y.data_ptr(), g.ldy, *cptrs, sums.data_ptr(), count, sv.w2.data_ptr(), sv.out.data_ptr(),
+         dout.data_ptr(), dy.data_ptr(), g.ldy, tanh0, g.code, g.N, g.H * g.W, g.Cout, Co, g.stream)
+    return dy, g32, dhw, dhb
+
+
+def _dz_fused_pool(g: _Geom, st: BNState, ctx, sv, da, dpl):
+    """Pool + skip + BatchNorm backward, two passes over (y, dpl, dskip): no da tensor."""
+    slab, dy, cptrs = _dz_begin(g, sv)
+    dpl = _as_nhwc(dpl)
+    dsk = _as_nhwc(da) if da is not None else None
+    pargs = (sv.y.data_ptr(), g.ldy, dpl.data_ptr(), _ld(dpl), sv.argidx.data_ptr(), _ptr(dsk), _ld(dsk) if dsk is not None else 0)
+    call("mau_pool_bn_bwd_reduce", *pargs, *cptrs, slab.data_ptr(), g.Cout, g.code, g.N, g.H, g.W, g.Cout, g.stream)
+    sums, count, g32 = _finish_sums(g, st, slab)
+    call("mau_pool_bn_bwd_apply", *pargs, *cptrs, sums.data_ptr(), count, dy.data_ptr(), g.ldy, g.code, g.N, g.H, g.W, g.Cout, g.stream)
+    return dy, g32, None, None
+
+
+def _dz_generic(g: _Geom, st: BNState, ctx, sv, da, dpl):
+    """BatchNorm + ReLU backward, two passes over (da, y), behind whatever produces da from the layer's output gradients."""
+    y, ldy, npix, stream = sv.y, g.ldy, g.N * g.H * g.W, g.stream
+    slab, dy, cptrs = _dz_begin(g, sv)
+    dhw = dhb = None
+    if ctx.head is not None:
+        # unfused head: da, dW, db from the saved activation
+        _, tanh0, hshape, _ = ctx.head
+        da, dhw, dhb = _head_bwd(sv.a, g.Cout, sv.w2, sv.out, da, tanh0, hshape, stream)
+    elif ctx.up is not None:
+        # the upsample's adjoint produces da (its forward read y through BatchNorm + ReLU, or the activation)
+        da = _resize_bwd(_as_nhwc(da), 0, g.Cout, (g.H, g.W), stream)
+    elif ctx.pooled and dpl is not None:
+        # the block's output fed the pool AND the skip connection: one pass adds the two gradients (PoolSkip's job)
+        act = sv.a
+        if act is None:                          # (fused build, but this backward runs unfused: recompute the activation)
+            act = torch.empty_like(y)
+            call("mau_bn_relu_apply", y.data_ptr(), ldy, sv.scale.data_ptr(), sv.shift.data_ptr(), act.data_ptr(), ldy, g.code, npix, g.Cout, stream)
+        da = _pool_bwd(act, g.Cout, dpl, da, stream)
+    elif da is None:
+        da = torch.zeros((g.N, g.H, g.W, ldy), dtype=y.dtype, device=g.dev)
+    da = _as_nhwc(da)
+    call("mau_bn_relu_bwd_reduce", da.data_ptr(), _ld(da), y.data_ptr(), ldy, *cptrs, slab.data_ptr(), g.Cout, g.code, npix, g.Cout, stream)
+    sums, count, g32 = _finish_sums(g, st, slab)
+    call("mau_bn_relu_bwd_apply", da.data_ptr(), _ld(da), y.data_ptr(), ldy, *cptrs, sums.data_ptr(), count, dy.data_ptr(), ldy, g.code, npix, g.Cout, stream)
+    return dy, g32, dhw, dhb
+
+
+def _dgrad_launch(g: _Geom, dy, wd, weight):
+    """The data gradient w.r.t. cat([x, x1, broadcast(emb)], channels): the same implicit-GEMM kernel on dy with the rotated /
+    transposed weight pack (``wd``: the forward's, or None = pack now)."""
+    if wd is None:
+        wd = pack_conv_weights(weight, g.code, forward=False, dgrad=True)[1]
+    ldd = pad8(g.Cin)
+    dfull = torch.empty((g.N, g.H, g.W, ldd), dtype=g.act_dt, device=g.dev)
+    call("mau_conv3x3_fwd", dy.data_ptr(), g.ldy, g.Cout, None, None, 0, wd.data_ptr(), None, None, None, dfull.data_ptr(), ldd, g.Cin, None,
+         g.code, g.N, g.H, g.W, g.stream)
+    return dfull
+
+
+def _conv_wgrad(g: _Geom, st: BNState, sv, E, C1, dy, side, overlap, waits_for_dy):
+    """The weight gradient, on ``side`` if given (``waits_for_dy``: the side stream already waits for dy).  Returns (dw, whether
+    the join with the side stream is left to the end of the backward pass)."""
+    x, x1, emb, weight = sv.x, sv.x1, sv.emb, sv.weight
+    if side is not None and not waits_for_dy:
+        side.wait_stream(torch.cuda.current_stream())           # dy is complete
+    with torch.cuda.stream(side) if side is not None else contextlib.nullcontext():
+        # (workspaces of the side stream's kernels belong to ITS allocator pool: freed here, re-used there)
+        acc = torch.empty(max(lib.mau_conv3x3_wgrad_acc_elems(g.code, g.N, g.H, g.W, g.Cout, g.Cin),
+                              lib.mau_conv3x3_first_wgrad_ws_elems(g.N, g.H, g.W, g.Cout) if st.first else 0), dtype=torch.float32, device=g.dev)
+        emb_ws = torch.empty((g.N, E), dtype=g.act_dt, device=g.dev) if E else None
+    # data parallel (dist.GradSync): the split-K sum is written straight into the parameter's slot of the gradient arena
+    # and autograd adopts the returned view as weight.grad -- no copy into the arena later.  Only for the FIRST
+    # gradient of a step: an accumulating backward (weight.grad already set) must not overwrite what it adds to.
+    slot = getattr(weight, "_mau_grad_slot", None)
+    dw = slot.view_as(weight) if (slot is not None and weight.is_leaf and weight.grad is None and slot.device == g.dev) else torch.empty_like(weight)
+    wstream = side.cuda_stream if side is not None else g.stream
+    # deferred join: only where the gradient is ASSIGNED (arena slot adopted as weight.grad, or a fresh tensor) -- an
+    # accumulating AccumulateGrad would add on the main stream to what the side stream is still writing
+    # (and only for a parameter: the gradient of a derived weight -- EmbFold's W_eff -- is read by ITS backward on the main stream)
+    deferred = side is not None and overlap >= 2 and weight.is_leaf and weight.grad is None
+    if st.first and _FIRST_WGRAD:
+        # conv0_0.conv1: K = pixels, N = 9 taps x 8 channels straight from the forward's NHWC-8 by-product (csrc/conv3x3_first.hip)
+        call("mau_conv3x3_first_wgrad", x.data_ptr(), dy.data_ptr(), g.ldy, dw.data_ptr(), acc.data_ptr(), g.Cin, g.Cout, g.code, g.N, g.H, g.W, wstream)
+    else:
+        call("mau_conv3x3_wgrad2", x.data_ptr(), _ld(x), st.C0, _ptr(x1), _ld(x1) if x1 is not None else 0, C1,
+             emb.data_ptr() if E else None, emb_ws.data_ptr() if E else None, E, dy.data_ptr(), g.ldy, g.Cout, acc.data_ptr(),
+             g.code, g.N, g.H, g.W, wstream)
+        call("mau_conv3x3_unpack_wgrad", acc.data_ptr(), lib.mau_conv3x3_wgrad_splits(g.code, g.N, g.H, g.W, g.Cout, g.Cin),
+             dw.data_ptr(), g.Cout, g.Cin, wstream)
+    if deferred:
+        for t in (x, x1, emb, dy, dw):                           # read / written over there after this function has returned
+            if t is not None:
+                t.record_stream(side)
+        weight._mau_grad_stream = side                           # (dist.GradSync: the bucket's launch waits for it)
+        _join_side_when_backward_ends(g.dev)
+    return dw, deferred
+
+
+def _conv_dgrad(g: _Geom, st: BNState, E, C1, dfull, needs):
+    """The inputs' gradients out of the data gradient ``dfull`` -> (dx, dx1, demb)."""
+    dx = dx1 = demb = None
+    if E and needs[2]:
+        demb = torch.empty((g.N, E), dtype=torch.float32, device=g.dev)
+        ws = torch.empty(lib.mau_bcast_bwd_ws_elems(g.N, g.H * g.W, E), dtype=torch.float32, device=g.dev)
+        call("mau_bcast_bwd", dfull.data_ptr(), pad8(g.Cin), st.C0 + C1, demb.data_ptr(), ws.data_ptr(), g.code, g.N, g.H * g.W, E, g.stream)
+    if C1:
+        # the two tensors' gradients are channel slices of one buffer (C0 % 16 == 0; with E > 0 also C1 % 8 == 0)
+        if needs[0]:
+            dx = dfull[..., :st.C0]
+        if needs[1]:
+            dx1 = dfull[..., st.C0:st.C0 + pad8(C1)]
+    elif needs[0]:
+        dx = dfull[..., :pad8(st.C0)] if E else dfull           # C0 % 8 == 0 is enforced by the kernel when E > 0
+    return dx, dx1, demb
 
 
 class ConvBNReLU(torch.autograd.Function):
@@ -406,334 +814,49 @@ class ConvBNReLU(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x, x1, emb, weight, bias, gamma, beta, rmean, rvar, nbt, hw, hb, st: BNState):
-        _require_cuda(x, "conv3x3")
-        first = st.first
-        if first:
-            # the network's first convolution on the input tensor as delivered (src/model.py:222, src/dataset.py:99-106)
-            if x1 is not None or emb is not None or x.dim() != 4 or x.shape[1] != st.C0 or st.C0 > lib.mau_conv3x3_first_max_channels():
-                raise RuntimeError("conv3x3 (first layer): expects one (N, C <= 8, H, W) fp32 input")
-            xin = x.contiguous().float()
-            N, _, H, W = xin.shape
-            act_dt = st.dtype
-        else:
-            x = _as_nhwc(x)
-            if x1 is not None:
-                x1 = _as_nhwc(x1)
-            N, H, W, _ = x.shape
-            act_dt = x.dtype
-        code = dtype_code(act_dt)
-        dev = x.device
-        Cout, Cin = weight.shape[0], weight.shape[1]
-        E = 0 if emb is None else emb.shape[1]
-        C1 = st.C1 if x1 is not None else 0
-        if st.C0 + C1 + E != Cin:
-            raise RuntimeError(f"conv3x3: input has {st.C0}+{C1}+{E} channels, weight expects {Cin}")
-        if emb is not None:
-            emb = emb.contiguous().float()
-        ldy = pad8(Cout)
-        stream = _stream()
+        g, src, head = _conv_inputs(x, x1, emb, weight, hw, st)
         needs = ctx.needs_input_grad
-        inference = (not st.training) and (not st.grad_enabled or not any(needs))
-        emb_ws = torch.empty((N, E), dtype=act_dt, device=dev) if E else None
-        f32 = dict(dtype=torch.float32, device=dev)
-        dst = st.out_view                               # where the activation goes: a slot of a row buffer, or a fresh tensor
-        if dst is not None and (tuple(dst.shape) != (N, H, W, ldy) or dst.dtype != act_dt or Cout % 64 != 0):
-            raise RuntimeError("conv3x3: out_view must be an (N,H,W,Cout) NHWC-ld view of the activation dtype with Cout % 64 == 0")
-        if sum((st.pool, st.head is not None, st.up_to is not None)) > 1 or ((st.head is not None or st.up_to is not None) and dst is not None):
-            raise RuntimeError("conv3x3: pool / head / up_to are exclusive, and head / up_to write no activation (no out_view)")
-        Co = tanh0 = 0
-        w2 = None
-        if st.head is not None:
-            Co = hw.shape[0]
-            tanh0 = 1 if (Co == 2 and st.head) else 0
-            w2 = hw.detach().reshape(Co, Cout).contiguous().float()
-
-        def first_fwd(post, y_, slab_, x8_):
-            """conv0_0.conv1 straight from the fp32 NCHW input and the fp32 master weights (no layout kernel, no weight pack)"""
-            scale_, shift_ = post if post is not None else (None, None)
-            call("mau_conv3x3_first_fwd", xin.data_ptr(), st.C0, weight.detach().data_ptr(), bias.detach().data_ptr() if bias is not None else None,
-                 scale_.data_ptr() if scale_ is not None else None, shift_.data_ptr() if shift_ is not None else None, y_.data_ptr(), _ld(y_),
-                 Cout, slab_.data_ptr() if slab_ is not None else None, x8_.data_ptr() if x8_ is not None else None, code, N, H, W, stream)
-
-        def pooled_of(a):
-            pl = torch.empty((N, H // 2, W // 2, ldy), dtype=act_dt, device=dev)
-            call("mau_maxpool2x2_fwd", a.data_ptr(), _ld(a), pl.data_ptr(), ldy, code, N, H, W, Cout, stream)
-            return pl
-
-        def head_of(a):                                 # final 1x1 conv (+ tanh on channel 0) of a materialised activation
-            out = torch.empty((N, Co, H, W), **f32)
-            call("mau_head_fwd", a.data_ptr(), _ld(a), w2.data_ptr(), hb.detach().data_ptr(), out.data_ptr(), tanh0, code, N, H * W,
-                 Cout, Co, stream)
-            return out
-
-        def up_of(a):                                   # bilinear resize of a materialised activation
-            Hu, Wu = st.up_to
-            up = torch.empty((N, Hu, Wu, ldy), dtype=act_dt, device=dev)
-            call("mau_resize_bilinear_fwd", a.data_ptr(), _ld(a), H, W, up.data_ptr(), ldy, 0, code, N, Hu, Wu, Cout, stream)
-            return up
-
-        if inference:
-            # eval-mode BN + ReLU are a fixed per-channel affine map -> folded into the conv epilogue.  In a frozen
-            # session (UrbanPredictor.freeze_inference) the packed weights and the folded coefficients are computed once.
-            y = dst if dst is not None else torch.empty((N, H, W, ldy), dtype=act_dt, device=dev)
-            fz = st.frozen if st.frozen is not None else {}
-            fkey = (_GENERATION[0], weight._version, gamma._version, rmean._version, rvar._version)
-            if "wf" not in fz or fz["wf"].dtype != act_dt or fz.get("key") != fkey:
-                # (an optimizer step -- of ANY model: the generation counter is global --, mark_params_updated() or an in-place
-                #  write re-derives the copies.)  Everything is refreshed IN PLACE: the packs are persistent buffers and
-                # scale / shift are allocated once per session, so a live GraphedInference graph, which holds these
-                # addresses, replays with the new values instead of reading freed memory.
-                fz["key"] = fkey
-                fz["wf"] = weight if first else pack_conv_weights(weight, code, forward=True, dgrad=False)[0]     # (first layer: the master weights themselves)
-                if "scale" not in fz or fz["scale"].device != dev or fz["scale"].numel() != Cout:
-                    fz["scale"], fz["shift"] = torch.empty(Cout, **f32), torch.empty(Cout, **f32)
-                call("mau_bn_coeffs_eval", gamma.data_ptr(), beta.data_ptr(), rmean.data_ptr(), rvar.data_ptr(),
-                     st.eps, fz["scale"].data_ptr(), fz["shift"].data_ptr(), None, None, Cout, stream)
-            pl = None
-            if first:
-                first_fwd((fz["scale"], fz["shift"]), y, None, None)
-            elif st.pool and _INFER_POOL_FUSED and x1 is None and not E and H >= 2 and W >= 2:
-                # an encoder block's second convolution: the pooled tensor comes out of the same launch (the 16x16x32 tilings take the
-                # 2x2 maxima from the registers they store; other tilings run the pooling kernel behind the convolution inside the call)
-                pl = torch.empty((N, H // 2, W // 2, ldy), dtype=act_dt, device=dev)
-                call("mau_conv3x3_fwd_pool", x.data_ptr(), _ld(x), st.C0, fz["wf"].data_ptr(), bias.data_ptr() if bias is not None else None,
-                     fz["scale"].data_ptr(), fz["shift"].data_ptr(), y.data_ptr(), _ld(y), Cout, pl.data_ptr(), ldy, code, N, H, W, stream)
-            else:
-                _conv_fwd(x, x1, st, emb, emb_ws, E, fz["wf"], bias, (fz["scale"], fz["shift"]), y, Cout, None, code, N, H, W, stream)
-            if st.head is not None:
-                out = head_of(y)
-                ctx.mark_non_differentiable(out)
-                return out
-            if st.up_to is not None:
-                up = up_of(y)
-                ctx.mark_non_differentiable(up)
-                return up
-            ctx.mark_non_differentiable(y)
-            if st.pool:
-                if pl is None:
-                    pl = pooled_of(y)
-                ctx.mark_non_differentiable(pl)
-                return y, pl
-            return y
-        y = torch.empty((N, H, W, ldy), dtype=act_dt, device=dev)
-        need_dx = needs[0] or (x1 is not None and needs[1]) or (E > 0 and needs[2])
-        if first:
+        bn = (gamma, beta, rmean, rvar, nbt)
+        if (not st.training) and (not st.grad_enabled or not any(needs)):
+            outs = _conv_inference(g, st, src, weight, bias, bn, head, hb)
+            ctx.mark_non_differentiable(*outs)
+            return outs if st.pool else outs[0]
+        need_dx = needs[0] or (src[1] is not None and needs[1]) or (src[3] is not None and needs[2])      # (emb_ws: E > 0)
+        if st.first:
             if need_dx:
                 raise RuntimeError("conv3x3 (first layer): no gradient w.r.t. the network input on this path")
-            wf = wd = None
+            w, wd = weight, None
             # the input in the activation type as NHWC-8: what this layer's weight gradient reads; a by-product of the same pass
-            x = torch.empty((N, H, W, 8), dtype=act_dt, device=dev) if (st.grad_enabled and needs[3]) else None
+            x8 = torch.empty((g.N, g.H, g.W, 8), dtype=g.act_dt, device=g.dev) if (st.grad_enabled and needs[3]) else None
+            saved_src = (x8, None, None, None)
         else:
-            wf, wd = pack_conv_weights(weight, code, forward=True, dgrad=st.grad_enabled and need_dx)
-        scale, shift = torch.empty(Cout, **f32), torch.empty(Cout, **f32)
-        mean, invstd = torch.empty(Cout, **f32), torch.empty(Cout, **f32)
-        npix = N * H * W
-        if st.training:
-            tiles = lib.mau_conv3x3_first_rows(N, H, W) if first else lib.mau_conv3x3_num_pixel_tiles(code, N, H, W, Cout)
-            cpad = (Cout + 63) // 64 * 64
-            slab = torch.empty((tiles, 2 * cpad), **f32)
-            if first:
-                first_fwd(None, y, slab, x)
-            else:
-                _conv_fwd(x, x1, st, emb, emb_ws, E, wf, bias, None, y, Cout, slab, code, N, H, W, stream)
-            nbt_ptr = nbt.data_ptr() if nbt is not None else None
-            tk = _tickets(dev).data_ptr() if _FUSED_REDUCE else None
-            if st.group is None:
-                # single GPU: slab -> fp64 partials -> second level + finalize by the last workgroup, ONE launch
-                ws = torch.empty(lib.mau_bn_stats_ws_elems(tiles, Cout), dtype=torch.float64, device=dev)
-                call("mau_bn_stats_finalize_train", slab.data_ptr(), tiles, float(npix), gamma.data_ptr(), beta.data_ptr(),
-                     rmean.data_ptr(), rvar.data_ptr(), nbt_ptr, st.momentum, st.eps, scale.data_ptr(), shift.data_ptr(),
-                     mean.data_ptr(), invstd.data_ptr(), ws.data_ptr(), tk, Cout, stream)
-            else:
-                # SyncBN: ONE collective per layer carries [sum(y) | sum(y^2) | local pixel count]; the count is summed
-                # with the statistics, so ranks with different local batch sizes still agree on the global moments
-                sums = torch.empty(2 * Cout + 1, dtype=torch.float64, device=dev)
-                ws = torch.empty(lib.mau_reduce_rows_ws_elems(tiles, 2 * Cout), dtype=torch.float64, device=dev)
-                call("mau_bn_stats_sums_f64", slab.data_ptr(), tiles, Cout, sums.data_ptr(), ws.data_ptr(), _tickets(dev).data_ptr(),
-                     float(npix), stream)
-                _all_reduce_(sums, st)
-                call("mau_bn_finalize_train", sums.data_ptr(), 0.0, gamma.data_ptr(), beta.data_ptr(),
-                     rmean.data_ptr(), rvar.data_ptr(), nbt_ptr, st.momentum, st.eps, scale.data_ptr(), shift.data_ptr(),
-                     mean.data_ptr(), invstd.data_ptr(), Cout, stream)
-        else:
-            call("mau_bn_coeffs_eval", gamma.data_ptr(), beta.data_ptr(), rmean.data_ptr(), rvar.data_ptr(),
-                 st.eps, scale.data_ptr(), shift.data_ptr(), mean.data_ptr(), invstd.data_ptr(), Cout, stream)
-            if first:
-                first_fwd(None, y, None, x)
-            else:
-                _conv_fwd(x, x1, st, emb, emb_ws, E, wf, bias, None, y, Cout, None, code, N, H, W, stream)
-
-        # ---- the activation stage ----
-        fused = _FUSED_BN
-        fuse_head = fused and st.head is not None and Cout <= lib.mau_head_bn_max_channels() and H * W >= 32
-        fuse_up = fused and _FUSED_UP and st.up_to is not None and H <= st.up_to[0] and W <= st.up_to[1]
-        a = pl = out = up = argidx = None
-        if fuse_head:                                    # the head reads y and applies BatchNorm + ReLU on the fly: no activation tensor
-            out = torch.empty((N, Co, H, W), **f32)
-            call("mau_head_bn_fwd", y.data_ptr(), ldy, scale.data_ptr(), shift.data_ptr(), w2.data_ptr(), hb.detach().data_ptr(),
-                 out.data_ptr(), tanh0, code, N, H * W, Cout, Co, stream)
-        elif fuse_up:                                    # the resize applies BatchNorm + ReLU to the corners it loads
-            Hu, Wu = st.up_to
-            up = torch.empty((N, Hu, Wu, ldy), dtype=act_dt, device=dev)
-            call("mau_resize_bilinear_bn_fwd", y.data_ptr(), ldy, H, W, scale.data_ptr(), shift.data_ptr(), up.data_ptr(), ldy, 0, code,
-                 N, Hu, Wu, Cout, stream)
-        else:
-            a = dst if dst is not None else torch.empty_like(y)
-            lda = _ld(a)
-            if st.pool and H >= 2 and W >= 2:
-                pl = torch.empty((N, H // 2, W // 2, ldy), dtype=act_dt, device=dev)
-                # 2 bits per (window, channel): which pixel holds the maximum -- the routing of the pool's backward (fused with the
-                # BatchNorm backward passes, no activation is re-read for it)
-                argidx = torch.empty((N, H // 2, W // 2, ldy // 8), dtype=torch.int16, device=dev) if fused else None
-                call("mau_bn_relu_apply_pool", y.data_ptr(), ldy, scale.data_ptr(), shift.data_ptr(), a.data_ptr(), lda,
-                     pl.data_ptr(), ldy, argidx.data_ptr() if argidx is not None else None, code, N, H, W, Cout, stream)
-            else:
-                call("mau_bn_relu_apply", y.data_ptr(), ldy, scale.data_ptr(), shift.data_ptr(), a.data_ptr(), lda, code,
-                     npix, Cout, stream)
-            if st.head is not None:
-                out = head_of(a)
-            elif st.up_to is not None:
-                up = up_of(a)
-        # (the context must not hold the output: st.out_view IS the returned activation, and node -> ctx -> st -> out_view -> grad_fn
-        #  -> node is a reference cycle that only Python's cycle collector frees -- a whole step's graph, its AccumulateGrad nodes
-        #  included, then outlives the step; a hipGraph capture that meets those stale nodes dies in hipStreamEndCapture)
-        ctx.st = st if st.out_view is None else dataclasses.replace(st, out_view=None)
-        ctx.E = E
-        ctx.C1 = C1
-        ctx.wd = wd                           # data-gradient pack of THIS forward's weights
-        ctx.pooled = pl is not None
-        ctx.head = (Co, tanh0, tuple(hw.shape), fuse_head) if st.head is not None else None
-        ctx.up = (st.up_to, fuse_up) if st.up_to is not None else None
-        # the activation is saved only where the backward still reads it: the unfused pool (arg-max) and the unfused head (dW)
-        keep_a = a if ((pl is not None and not fused) or (st.head is not None and not fuse_head)) else None
-        ctx.save_for_backward(x, x1, emb, weight, y, scale, shift, mean, invstd, keep_a, w2, out, argidx)
-        if st.head is not None:
-            return out
-        if st.up_to is not None:
-            return up
-        if st.pool:
-            return a, pl
-        return a
+            w, wd = pack_conv_weights(weight, g.code, forward=True, dgrad=st.grad_enabled and need_dx)
+            x8, saved_src = None, src
+        y, coef = _conv_with_stats(g, st, src, w, bias, bn, x8)
+        outs, kept, fused = _conv_activation(g, st, y, coef[0], coef[1], head, hb)
+        _conv_save(ctx, st, saved_src, weight, wd, y, coef, head, hw, outs, kept, fused)
+        return outs if st.pool else outs[0]
 
     @staticmethod
     def backward(ctx, da, dpl=None):
-        x, x1, emb, weight, y, scale, shift, mean, invstd, a, w2, out, argidx = ctx.saved_tensors
+        sv = _Saved(*ctx.saved_tensors)
         st: BNState = ctx.st
-        E, C1 = ctx.E, ctx.C1
+        E, C1 = (0 if sv.emb is None else sv.emb.shape[1]), (st.C1 if sv.x1 is not None else 0)
+        y, weight = sv.y, sv.weight
         N, H, W, ldy = y.shape
-        code = dtype_code(y.dtype)
-        dev = y.device
-        Cout, Cin = weight.shape[0], weight.shape[1]
-        npix = N * H * W
-        stream = _stream()
-        f32 = dict(dtype=torch.float32, device=dev)
+        Cout = weight.shape[0]
+        g = _Geom(N, H, W, weight.shape[1], Cout, ldy, dtype_code(y.dtype), y.dtype, y.device, _stream())
         needs = ctx.needs_input_grad
-        sync = st.training and st.group is not None
-        rows = lib.mau_bn_bwd_rows(npix)
-        slab = torch.empty((rows, 2 * Cout), **f32)
-        sums = torch.empty(2 * Cout + 1, dtype=torch.float64, device=dev)
-        g32 = torch.empty(2 * Cout, **f32)                   # [dbeta | dgamma]: the LOCAL sums, rounded to fp32 by the reducer
-        dy = torch.empty_like(y)
-        dhw = dhb = None
-        cptrs = (scale.data_ptr(), shift.data_ptr(), mean.data_ptr(), invstd.data_ptr())
-
-        def finish_sums():
-            """slab -> sums (fp64) + g32 (fp32), one launch; data parallel: all-reduce with the pixel count appended.
-            Returns (sums for the apply pass, count argument)."""
-            ws = torch.empty(lib.mau_reduce_rows_ws_elems(rows, 2 * Cout), dtype=torch.float64, device=dev)
-            call("mau_reduce_rows_f64_f32", slab.data_ptr(), rows, 2 * Cout, 2 * Cout, sums.data_ptr(), g32.data_ptr(), ws.data_ptr(),
-                 _tickets(dev).data_ptr() if (_FUSED_REDUCE or sync) else None, float(npix) if sync else 0.0, stream)
-            if not st.training:
-                return torch.zeros_like(sums), float(npix)       # eval-mode BN is a fixed affine map
-            if sync:                                             # the global count travels with the sums (see forward)
-                _all_reduce_(sums, st)
-                return sums, 0.0
-            return sums, float(npix)
-
-        fused_pool = ctx.pooled and dpl is not None and argidx is not None
-        if ctx.head is not None and ctx.head[3]:
-            # ---- head + BatchNorm backward, two passes over y: da = W_head^T dz is recomputed from dout in both ----
-            Co, tanh0, hshape, _ = ctx.head
-            dout = da.contiguous().float()
-            hrows, rowlen = lib.mau_head_bwd_rows(N, H * W), lib.mau_head_bwd_rowlen(Cout, Co)
-            hslab = torch.empty((hrows, rowlen), **f32)
-            call("mau_head_bn_bwd_reduce", y.data_ptr(), ldy, *cptrs, w2.data_ptr(), out.data_ptr(), dout.data_ptr(), slab.data_ptr(), Cout,
-                 hslab.data_ptr(), tanh0, code, N, H * W, Cout, Co, stream)
-            sums_apply, count = finish_sums()
-            red = torch.empty(rowlen, **f32)
-            hws = torch.empty(lib.mau_reduce_rows_ws_elems(hrows, rowlen), dtype=torch.float64, device=dev)
-            call("mau_reduce_rows_f32", hslab.data_ptr(), hrows, rowlen, rowlen, red.data_ptr(), hws.data_ptr(),
-                 _tickets(dev).data_ptr() if _FUSED_REDUCE else None, stream)
-            red = red.view(Co, pad8(Cout) + 8)
-            dhw = red[:, :Cout].reshape(hshape).contiguous()
-            dhb = red[:, pad8(Cout)].contiguous()
-            call("mau_head_bn_bwd_apply", y.data_ptr(), ldy, *cptrs, sums_apply.data_ptr(), count, w2.data_ptr(), out.data_ptr(),
-                 dout.data_ptr(), dy.data_ptr(), ldy, tanh0, code, N, H * W, Cout, Co, stream)
-        elif fused_pool:
-            # ---- pool + skip + BatchNorm backward, two passes over (y, dpl, dskip): no da tensor ----
-            dpl = _as_nhwc(dpl)
-            dsk = _as_nhwc(da) if da is not None else None
-            pargs = (y.data_ptr(), ldy, dpl.data_ptr(), _ld(dpl), argidx.data_ptr(), dsk.data_ptr() if dsk is not None else None,
-                     _ld(dsk) if dsk is not None else 0)
-            call("mau_pool_bn_bwd_reduce", *pargs, *cptrs, slab.data_ptr(), Cout, code, N, H, W, Cout, stream)
-            sums_apply, count = finish_sums()
-            call("mau_pool_bn_bwd_apply", *pargs, *cptrs, sums_apply.data_ptr(), count, dy.data_ptr(), ldy, code, N, H, W, Cout, stream)
-        else:
-            if ctx.head is not None:
-                # unfused head: da, dW, db from the saved activation
-                Co, tanh0, hshape, _ = ctx.head
-                dout = da.contiguous().float()
-                da = torch.empty((N, H, W, ldy), dtype=y.dtype, device=dev)
-                hrows, rowlen = lib.mau_head_bwd_rows(N, H * W), lib.mau_head_bwd_rowlen(Cout, Co)
-                hslab = torch.empty((hrows, rowlen), **f32)
-                call("mau_head_bwd", a.data_ptr(), _ld(a), w2.data_ptr(), out.data_ptr(), dout.data_ptr(), da.data_ptr(), ldy,
-                     hslab.data_ptr(), tanh0, code, N, H * W, Cout, Co, stream)
-                red = torch.empty(rowlen, **f32)
-                hws = torch.empty(lib.mau_reduce_rows_ws_elems(hrows, rowlen), dtype=torch.float64, device=dev)
-                call("mau_reduce_rows_f32", hslab.data_ptr(), hrows, rowlen, rowlen, red.data_ptr(), hws.data_ptr(),
-                     _tickets(dev).data_ptr() if _FUSED_REDUCE else None, stream)
-                red = red.view(Co, pad8(Cout) + 8)
-                dhw = red[:, :Cout].reshape(hshape).contiguous()
-                dhb = red[:, pad8(Cout)].contiguous()
-            elif ctx.up is not None:
-                # the upsample's adjoint produces da (its forward read y through BatchNorm + ReLU, or the activation)
-                (Hu, Wu), _ = ctx.up
-                g = _as_nhwc(da)
-                da = torch.empty((N, H, W, ldy), dtype=y.dtype, device=dev)
-                call("mau_resize_bilinear_bwd", g.data_ptr(), _ld(g), 0, Hu, Wu, da.data_ptr(), ldy, code, N, H, W, Cout, stream)
-            elif ctx.pooled and dpl is not None:
-                # the block's output fed the pool AND the skip connection: one pass adds the two gradients (PoolSkip's job)
-                dpl = _as_nhwc(dpl)
-                act = a
-                if act is None:                          # (fused build, but this backward runs unfused: recompute the activation)
-                    act = torch.empty_like(y)
-                    call("mau_bn_relu_apply", y.data_ptr(), ldy, scale.data_ptr(), shift.data_ptr(), act.data_ptr(), ldy, code, npix, Cout, stream)
-                dsum = torch.empty((N, H, W, ldy), dtype=y.dtype, device=dev)
-                if da is None:
-                    call("mau_maxpool2x2_bwd", act.data_ptr(), _ld(act), dpl.data_ptr(), _ld(dpl), dsum.data_ptr(), ldy, code, N, H, W, Cout, stream)
-                else:
-                    da = _as_nhwc(da)
-                    call("mau_maxpool2x2_bwd_add", act.data_ptr(), _ld(act), dpl.data_ptr(), _ld(dpl), da.data_ptr(), _ld(da),
-                         dsum.data_ptr(), ldy, code, N, H, W, Cout, stream)
-                da = dsum
-            elif da is None:
-                da = torch.zeros((N, H, W, ldy), dtype=y.dtype, device=dev)
-            da = _as_nhwc(da)
-            # --- BN + ReLU backward: two passes over (da, y) ---
-            call("mau_bn_relu_bwd_reduce", da.data_ptr(), _ld(da), y.data_ptr(), ldy, *cptrs, slab.data_ptr(), Cout, code, npix, Cout, stream)
-            sums_apply, count = finish_sums()
-            call("mau_bn_relu_bwd_apply", da.data_ptr(), _ld(da), y.data_ptr(), ldy, *cptrs, sums_apply.data_ptr(), count, dy.data_ptr(), ldy,
-                 code, npix, Cout, stream)
-        dgamma = g32[Cout:]
-        dbeta = g32[:Cout]
+        dz = (_dz_fused_head if (ctx.head is not None and ctx.head[3])
+              else _dz_fused_pool if (ctx.pooled and dpl is not None and sv.argidx is not None) else _dz_generic)
+        dy, g32, dhw, dhb = dz(g, st, ctx, sv, da, dpl)
+        dgamma, dbeta = g32[Cout:], g32[:Cout]
         # --- weight gradient: independent of the data gradient given dy ---
-        dw = None
-        need_dx = needs[0] or (x1 is not None and needs[1]) or (E and needs[2])
+        need_dx = needs[0] or (sv.x1 is not None and needs[1]) or (E and needs[2])
         # (under dist.GradSync the buckets' all-reduces run on a communication stream that waits for the side stream by itself:
         #  the compute stream is not held up, so the overlap stays on -- round 3 had to switch it off there)
         overlap = _OVERLAP_WGRAD
-        side = _side_stream(dev) if (needs[3] and overlap and (need_dx or overlap >= 2)) else None
-        deferred = False
+        side = _side_stream(g.dev) if (needs[3] and overlap and (need_dx or overlap >= 2)) else None
         dfull = None
         if (st.dgrad_first if _DGRAD_FIRST is None else _DGRAD_FIRST == "1") and need_dx and needs[3] and side is not None:
             # the main chain's data gradient is enqueued BEFORE the branch's weight gradient (both need only dy: whichever is
@@ -741,76 +864,19 @@ class ConvBNReLU(torch.autograd.Function):
             # the event is recorded in front of the data gradient.  Which order is faster depends on the network (model._Runtime).
             dy_ready = torch.cuda.Event()
             dy_ready.record()
-            wd = ctx.wd if ctx.wd is not None else pack_conv_weights(weight, code, forward=False, dgrad=True)[1]
-            dfull = torch.empty((N, H, W, pad8(Cin)), dtype=y.dtype, device=dev)
-            call("mau_conv3x3_fwd", dy.data_ptr(), ldy, Cout, None, None, 0, wd.data_ptr(), None, None, None, dfull.data_ptr(),
-                 pad8(Cin), Cin, None, code, N, H, W, stream)
+            dfull = _dgrad_launch(g, dy, ctx.wd, weight)
             side.wait_event(dy_ready)
-        if needs[3]:
-            if side is not None and dfull is None:
-                side.wait_stream(torch.cuda.current_stream())           # dy is complete
-            with torch.cuda.stream(side) if side is not None else contextlib.nullcontext():
-                # (workspaces of the side stream's kernels belong to ITS allocator pool: freed here, re-used there)
-                acc = torch.empty(max(lib.mau_conv3x3_wgrad_acc_elems(code, N, H, W, Cout, Cin),
-                                      lib.mau_conv3x3_first_wgrad_ws_elems(N, H, W, Cout) if st.first else 0), **f32)
-                emb_ws = torch.empty((N, E), dtype=y.dtype, device=dev) if E else None
-            # data parallel (dist.GradSync): the split-K sum is written straight into the parameter's slot of the gradient arena
-            # and autograd adopts the returned view as weight.grad -- no copy into the arena later.  Only for the FIRST
-            # gradient of a step: an accumulating backward (weight.grad already set) must not overwrite what it adds to.
-            slot = getattr(weight, "_mau_grad_slot", None)
-            dw = slot.view_as(weight) if (slot is not None and weight.is_leaf and weight.grad is None and slot.device == dev) else torch.empty_like(weight)
-            wstream = side.cuda_stream if side is not None else stream
-            # deferred join: only where the gradient is ASSIGNED (arena slot adopted as weight.grad, or a fresh tensor) -- an
-            # accumulating AccumulateGrad would add on the main stream to what the side stream is still writing
-            # (and only for a parameter: the gradient of a derived weight -- EmbFold's W_eff -- is read by ITS backward on the main stream)
-            deferred = side is not None and overlap >= 2 and weight.is_leaf and weight.grad is None
-            if st.first and _FIRST_WGRAD:
-                # conv0_0.conv1: K = pixels, N = 9 taps x 8 channels straight from the forward's NHWC-8 by-product (csrc/conv3x3_first.hip)
-                call("mau_conv3x3_first_wgrad", x.data_ptr(), dy.data_ptr(), ldy, dw.data_ptr(), acc.data_ptr(), Cin, Cout, code, N, H, W, wstream)
-            else:
-                call("mau_conv3x3_wgrad2", x.data_ptr(), _ld(x), st.C0, x1.data_ptr() if x1 is not None else None,
-                     _ld(x1) if x1 is not None else 0, C1, emb.data_ptr() if E else None,
-                     emb_ws.data_ptr() if E else None, E, dy.data_ptr(), ldy, Cout, acc.data_ptr(), code, N, H, W, wstream)
-                call("mau_conv3x3_unpack_wgrad", acc.data_ptr(), lib.mau_conv3x3_wgrad_splits(code, N, H, W, Cout, Cin),
-                     dw.data_ptr(), Cout, Cin, wstream)
-            if deferred:
-                for t in (x, x1, emb, dy, dw):                           # read / written over there after this function has returned
-                    if t is not None:
-                        t.record_stream(side)
-                weight._mau_grad_stream = side                           # (dist.GradSync: the bucket's launch waits for it)
-                _join_side_when_backward_ends(dev)
-        # --- data gradient (same implicit-GEMM kernel, rotated/transposed weight pack) ---
+        dw, deferred = _conv_wgrad(g, st, sv, E, C1, dy, side, overlap, dfull is not None) if needs[3] else (None, False)
         dx = dx1 = demb = None
         if need_dx:
-            wd = ctx.wd if ctx.wd is not None else pack_conv_weights(weight, code, forward=False, dgrad=True)[1]
-            ldd = pad8(Cin)
-            if dfull is None:
-                dfull = torch.empty((N, H, W, ldd), dtype=y.dtype, device=dev)
-                call("mau_conv3x3_fwd", dy.data_ptr(), ldy, Cout, None, None, 0, wd.data_ptr(), None, None, None, dfull.data_ptr(),
-                     ldd, Cin, None, code, N, H, W, stream)
-            Ct = st.C0 + C1
-            if E and needs[2]:
-                demb = torch.empty((N, E), **f32)
-                ws = torch.empty(lib.mau_bcast_bwd_ws_elems(N, H * W, E), **f32)
-                call("mau_bcast_bwd", dfull.data_ptr(), ldd, Ct, demb.data_ptr(), ws.data_ptr(), code, N, H * W, E, stream)
-            if C1:
-                # the two tensors' gradients are channel slices of one buffer (C0 % 16 == 0; with E > 0 also C1 % 8 == 0)
-                if needs[0]:
-                    dx = dfull[..., :st.C0]
-                if needs[1]:
-                    dx1 = dfull[..., st.C0:st.C0 + pad8(C1)]
-            elif needs[0]:
-                dx = dfull[..., :pad8(st.C0)] if E else dfull           # C0 % 8 == 0 is enforced by the kernel when E > 0
+            dx, dx1, demb = _conv_dgrad(g, st, E, C1, dfull if dfull is not None else _dgrad_launch(g, dy, ctx.wd, weight), needs)
         if side is not None and not deferred:
             torch.cuda.current_stream().wait_stream(side)
         dbias = None
         if needs[4]:
-            if st.training:
-                # conv bias followed by train-mode BN has an identically zero gradient (the batch mean absorbs it)
-                dbias = _zero_bias_grad(Cout, dev)
-            else:
-                # eval-mode BN is the fixed affine map z = scale*y + shift: d/dbias = sum(dy) = scale * sum(dz)
-                dbias = scale * dbeta
+            # train: a conv bias followed by train-mode BN has an identically zero gradient (the batch mean absorbs it);
+            # eval-mode BN is the fixed affine map z = scale*y + shift: d/dbias = sum(dy) = scale * sum(dz)
+            dbias = _zero_bias_grad(Cout, g.dev) if st.training else sv.scale * dbeta
         return dx, dx1, demb, dw, dbias, dgamma, dbeta, None, None, None, dhw, dhb, None
 
 
@@ -823,23 +889,14 @@ class MaxPool2x2(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, C):
         x = _as_nhwc(x)
-        N, H, W, _ = x.shape
-        ldy = pad8(C)
-        y = torch.empty((N, H // 2, W // 2, ldy), dtype=x.dtype, device=x.device)
-        call("mau_maxpool2x2_fwd", x.data_ptr(), _ld(x), y.data_ptr(), ldy, dtype_code(x.dtype), N, H, W, C, _stream())
         ctx.save_for_backward(x)
         ctx.C = C
-        return y
+        return _pool_fwd(x, C, _stream())
 
     @staticmethod
     def backward(ctx, dy):
         (x,) = ctx.saved_tensors
-        dy = _as_nhwc(dy)
-        N, H, W, _ = x.shape
-        dx = torch.empty((N, H, W, pad8(ctx.C)), dtype=x.dtype, device=x.device)
-        call("mau_maxpool2x2_bwd", x.data_ptr(), _ld(x), dy.data_ptr(), _ld(dy), dx.data_ptr(), pad8(ctx.C),
-             dtype_code(x.dtype), N, H, W, ctx.C, _stream())
-        return dx, None
+        return _pool_bwd(x, ctx.C, dy, None, _stream()), None
 
 
 class PoolSkip(torch.autograd.Function):
@@ -850,41 +907,27 @@ class PoolSkip(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, C):
         x = _as_nhwc(x)
-        N, H, W, _ = x.shape
-        ldy = pad8(C)
-        y = torch.empty((N, H // 2, W // 2, ldy), dtype=x.dtype, device=x.device)
-        call("mau_maxpool2x2_fwd", x.data_ptr(), _ld(x), y.data_ptr(), ldy, dtype_code(x.dtype), N, H, W, C, _stream())
         ctx.save_for_backward(x)
         ctx.C = C
-        return y, x.view_as(x)
+        return _pool_fwd(x, C, _stream()), x.view_as(x)
 
     @staticmethod
     def backward(ctx, dy, dskip):
         (x,) = ctx.saved_tensors
         if dy is None:
             return dskip, None
-        dy = _as_nhwc(dy)
-        N, H, W, _ = x.shape
-        dx = torch.empty((N, H, W, pad8(ctx.C)), dtype=x.dtype, device=x.device)
-        if dskip is None:
-            call("mau_maxpool2x2_bwd", x.data_ptr(), _ld(x), dy.data_ptr(), _ld(dy), dx.data_ptr(), pad8(ctx.C),
-                 dtype_code(x.dtype), N, H, W, ctx.C, _stream())
-        else:
-            dskip = _as_nhwc(dskip)
-            call("mau_maxpool2x2_bwd_add", x.data_ptr(), _ld(x), dy.data_ptr(), _ld(dy), dskip.data_ptr(), _ld(dskip),
-                 dx.data_ptr(), pad8(ctx.C), dtype_code(x.dtype), N, H, W, ctx.C, _stream())
-        return dx, None
+        return _pool_bwd(x, ctx.C, dy, dskip, _stream()), None
 
 
 # --------------------------------------------------------------------------- #
 # decoder input: cat([skips..., resize(low)]) on channels
 # --------------------------------------------------------------------------- #
-def _resize_into(src, Cs, h, w, dst, choff, N, H, W, code, stream):
+def _resize_into(src, Cs, dst, choff, code, stream):
+    N, H, W, _ = dst.shape
     if choff % 8 == 0:
-        call("mau_resize_bilinear_fwd", src.data_ptr(), _ld(src), h, w, dst.data_ptr(), _ld(dst), choff, code, N, H, W, Cs, stream)
+        _resize_fwd(src, Cs, (H, W), stream, dst, choff)
     else:   # tiny-channel models only: resize to a scratch tensor, then element-granular copy
-        tmp = torch.empty((N, H, W, pad8(Cs)), dtype=dst.dtype, device=dst.device)
-        call("mau_resize_bilinear_fwd", src.data_ptr(), _ld(src), h, w, tmp.data_ptr(), pad8(Cs), 0, code, N, H, W, Cs, stream)
+        tmp = _resize_fwd(src, Cs, (H, W), stream)
         call("mau_copy_channels", tmp.data_ptr(), pad8(Cs), dst.data_ptr(), _ld(dst), choff, 0, code, N * H * W, Cs, stream)
 
 
@@ -1037,36 +1080,20 @@ class UpsampleTo(torch.autograd.Function):
     def forward(ctx, low, C_low, two_step, H, W):
         low = _as_nhwc(low)
         N, h, w, _ = low.shape
-        code = dtype_code(low.dtype)
         stream = _stream()
-        ld = pad8(C_low)
-        src, sh, sw = low, h, w
-        mid = None
-        if two_step and (2 * h, 2 * w) != (H, W):
-            mid = torch.empty((N, 2 * h, 2 * w, ld), dtype=low.dtype, device=low.device)
-            call("mau_resize_bilinear_fwd", low.data_ptr(), _ld(low), h, w, mid.data_ptr(), ld, 0, code, N, 2 * h, 2 * w, C_low, stream)
-            src, sh, sw = mid, 2 * h, 2 * w
-        out = torch.empty((N, H, W, ld), dtype=low.dtype, device=low.device)
-        call("mau_resize_bilinear_fwd", src.data_ptr(), _ld(src), sh, sw, out.data_ptr(), ld, 0, code, N, H, W, C_low, stream)
-        ctx.meta = (C_low, (h, w), (H, W), mid is not None)
-        return out
+        two = two_step and (2 * h, 2 * w) != (H, W)
+        src = _resize_fwd(low, C_low, (2 * h, 2 * w), stream) if two else low
+        ctx.meta = (C_low, (h, w), (H, W), two)
+        return _resize_fwd(src, C_low, (H, W), stream)
 
     @staticmethod
     def backward(ctx, g):
-        C_low, (h, w), (H, W), two = ctx.meta
+        C_low, (h, w), _, two = ctx.meta
         g = _as_nhwc(g)
-        N = g.shape[0]
-        code = dtype_code(g.dtype)
         stream = _stream()
-        ld = pad8(C_low)
-        gsrc, gld, sH, sW = g, _ld(g), H, W
         if two:
-            dmid = torch.empty((N, 2 * h, 2 * w, ld), dtype=g.dtype, device=g.device)
-            call("mau_resize_bilinear_bwd", g.data_ptr(), gld, 0, H, W, dmid.data_ptr(), ld, code, N, 2 * h, 2 * w, C_low, stream)
-            gsrc, gld, sH, sW = dmid, ld, 2 * h, 2 * w
-        dlow = torch.empty((N, h, w, ld), dtype=g.dtype, device=g.device)
-        call("mau_resize_bilinear_bwd", gsrc.data_ptr(), gld, 0, sH, sW, dlow.data_ptr(), ld, code, N, h, w, C_low, stream)
-        return dlow, None, None, None, None
+            g = _resize_bwd(g, 0, C_low, (2 * h, 2 * w), stream)
+        return _resize_bwd(g, 0, C_low, (h, w), stream), None, None, None, None
 
 
 class ConcatUp(torch.autograd.Function):
@@ -1093,16 +1120,11 @@ class ConcatUp(torch.autograd.Function):
         for s, cs in zip(skips, skip_Cs):
             call("mau_copy_channels", s.data_ptr(), _ld(s), out.data_ptr(), ld, choff, 0, code, npix, cs, stream)
             choff += cs
-        mid = None
-        src, sh, sw = low, h, w
-        if two_step and (2 * h, 2 * w) != (H, W):
-            mid = torch.empty((N, 2 * h, 2 * w, pad8(C_low)), dtype=low.dtype, device=low.device)
-            call("mau_resize_bilinear_fwd", low.data_ptr(), _ld(low), h, w, mid.data_ptr(), pad8(C_low), 0, code, N, 2 * h, 2 * w, C_low, stream)
-            src, sh, sw = mid, 2 * h, 2 * w
-        _resize_into(src, C_low, sh, sw, out, choff, N, H, W, code, stream)
+        two = two_step and (2 * h, 2 * w) != (H, W)
+        _resize_into(_resize_fwd(low, C_low, (2 * h, 2 * w), stream) if two else low, C_low, out, choff, code, stream)
         if ld > Ctot:   # zero the pad channels
             out[..., Ctot:].zero_()
-        ctx.meta = (C_low, tuple(skip_Cs), (h, w), (H, W), mid is not None)
+        ctx.meta = (C_low, tuple(skip_Cs), (h, w), (H, W), two)
         return out
 
     @staticmethod
@@ -1126,21 +1148,14 @@ class ConcatUp(torch.autograd.Function):
                 grads.append(t)
             choff += cs
         if choff % 8 == 0:
-            gsrc, goff, gld = g, choff, ldg
+            gsrc, goff = g, choff
         else:
-            gsrc = torch.empty((N, H, W, pad8(C_low)), dtype=g.dtype, device=g.device)
+            gsrc, goff = torch.empty((N, H, W, pad8(C_low)), dtype=g.dtype, device=g.device), 0
             call("mau_copy_channels", g.data_ptr() + choff * g.element_size(), ldg, gsrc.data_ptr(), pad8(C_low), 0,
                  pad8(C_low), code, npix, C_low, stream)
-            goff, gld = 0, pad8(C_low)
         if two:
-            dmid = torch.empty((N, 2 * h, 2 * w, pad8(C_low)), dtype=g.dtype, device=g.device)
-            call("mau_resize_bilinear_bwd", gsrc.data_ptr(), gld, goff, H, W, dmid.data_ptr(), pad8(C_low), code, N, 2 * h, 2 * w, C_low, stream)
-            gsrc, goff, gld, sH, sW = dmid, 0, pad8(C_low), 2 * h, 2 * w
-        else:
-            sH, sW = H, W
-        dlow = torch.empty((N, h, w, pad8(C_low)), dtype=g.dtype, device=g.device)
-        call("mau_resize_bilinear_bwd", gsrc.data_ptr(), gld, goff, sH, sW, dlow.data_ptr(), pad8(C_low), code, N, h, w, C_low, stream)
-        return (dlow, None, None, None, *grads)
+            gsrc, goff = _resize_bwd(gsrc, goff, C_low, (2 * h, 2 * w), stream), 0
+        return (_resize_bwd(gsrc, goff, C_low, (h, w), stream), None, None, None, *grads)
 
 
 class BcastCat(torch.autograd.Function):
@@ -1190,13 +1205,10 @@ class Head(torch.autograd.Function):
     @staticmethod
     def forward(ctx, a, C, weight, bias, activate=True):
         a = _as_nhwc(a)
-        N, H, W, _ = a.shape
         Co = weight.shape[0]
         tanh0 = 1 if (Co == 2 and activate) else 0
-        out = torch.empty((N, Co, H, W), dtype=torch.float32, device=a.device)
         w2 = weight.detach().reshape(Co, C).contiguous().float()
-        call("mau_head_fwd", a.data_ptr(), _ld(a), w2.data_ptr(), bias.detach().data_ptr(), out.data_ptr(), tanh0,
-             dtype_code(a.dtype), N, H * W, C, Co, _stream())
+        out = _head_fwd(a, C, w2, bias, tanh0, _stream())
         ctx.save_for_backward(a, w2, out)
         ctx.meta = (C, Co, tanh0, tuple(weight.shape))
         return out
@@ -1204,22 +1216,8 @@ class Head(torch.autograd.Function):
     @staticmethod
     def backward(ctx, dout):
         a, w2, out = ctx.saved_tensors
-        C, Co, tanh0, wshape = ctx.meta
-        N, H, W, _ = a.shape
-        dout = dout.contiguous().float()
-        da = torch.empty((N, H, W, pad8(C)), dtype=a.dtype, device=a.device)
-        rows, rowlen = lib.mau_head_bwd_rows(N, H * W), lib.mau_head_bwd_rowlen(C, Co)
-        slab = torch.empty((rows, rowlen), dtype=torch.float32, device=a.device)   # (the 7 unwritten columns per output channel are never read back)
-        stream = _stream()
-        call("mau_head_bwd", a.data_ptr(), _ld(a), w2.data_ptr(), out.data_ptr(), dout.data_ptr(), da.data_ptr(), pad8(C),
-             slab.data_ptr(), tanh0, dtype_code(a.dtype), N, H * W, C, Co, stream)
-        red = torch.empty(rowlen, dtype=torch.float32, device=a.device)
-        ws = torch.empty(lib.mau_reduce_rows_ws_elems(rows, rowlen), dtype=torch.float64, device=a.device)
-        call("mau_reduce_rows_f32", slab.data_ptr(), rows, rowlen, rowlen, red.data_ptr(), ws.data_ptr(),
-             _tickets(a.device).data_ptr() if _FUSED_REDUCE else None, stream)
-        red = red.view(Co, pad8(C) + 8)
-        dw = red[:, :C].reshape(wshape).contiguous()
-        db = red[:, pad8(C)].contiguous()
+        C, _, tanh0, wshape = ctx.meta
+        da, dw, db = _head_bwd(a, C, w2, out, dout, tanh0, wshape, _stream())
         return da, None, dw, db, None
 
 
