@@ -610,6 +610,41 @@ size_t mau_tile_stats_ws_elems(int B, int64_t HW);
 int mau_tile_stats(const unsigned char* cls_a, const unsigned char* cls_b, const float* cont, const float* targets, double* rows,
                    double* ws, unsigned* tickets, int B, int64_t HW, int num_classes, mau_stream_t stream);
 
+/* ---- dataset build (src/data/processing_10m/process.py: the filter check and running statistics of :37-50 / :84-115, the
+ *      normalisation of :175-183): what the build needs from the pixels of a batch of RAW samples, ONE launch, every byte read
+ *      once.  Additive to ABI 5 ----
+ * dw_t1, dw_t2 (B,H,W) uint8 class maps; rgb (B,3,H,W) fp32, raw 0..255 values; ndvi_t1, ndvi_t2, temp_t1, temp_t2 (B,H,W) fp32;
+ * HW = H * W; num_classes in [1,16] (the dataset's layout: 9).  Three outputs, each optional (NULL skips it; cont and targets come
+ * together):
+ * rows (B) x mau_raw_tile_row_elems() = 38 fp64, per sample:
+ *   [0,16)   pixels where (dw_t1 == c) != (dw_t2 == c), per class c (0 for classes >= num_classes): count / HW is the reference's
+ *            per-channel mean |ohe2 - ohe1|                 [16], [17]  values >= num_classes in dw_t1, in dw_t2
+ *   [18] sum |ndvi_t2 - ndvi_t1|   [19] non-finite values of that difference   [20], [21] the same of temp_t2 - temp_t1: the
+ *            differences formed in fp64 from the loaded floats (exact) and never written to memory
+ *   [22 + 4p, 22 + 4p + 4)  the moment row  +0 n  +1 mean  +2 M2 = sum (x - mean)^2  +3 non-finite values  of p = 0..2: r / 255,
+ *            g / 255, b / 255 (the division in fp64), p = 3: temp_t1 -- two passes, not the reference's sum x^2 / n - mean^2.
+ * cont (B,5,H,W), targets (B,2,H,W) fp32, the layout mau_tile_stats and mau_pack_tile_onehot take; they need norm, 8 fp64 on the
+ * DEVICE: rgb_mean[3], rgb_std[3], temp_mean, temp_std.  numpy's arithmetic for float32 rasters, operation for operation, nothing
+ * contracted:
+ *   cont[0..2] = (float)(((double)rgb / 255.0 - mean_c) / std_c)     cont[3] = ndvi_t1, targets[0] = ndvi_t2, bits unchanged
+ *   cont[4], targets[1] = (t - (float)temp_mean) / (float)temp_std in fp32, the division correctly rounded.
+ * Geometry and order are mau_tile_stats': a workgroup owns 4096 consecutive pixels of ONE sample, sums in a fixed order, counts
+ * from ballots, no float atomics; the workgroup that draws the sample's last ticket merges the chunk rows in chunk order.  A
+ * row's bits and a plane's bits depend on the sample's own bytes only -- not on B, not on its place in the batch, not on which
+ * outputs were asked for -- and repeat.  A non-finite value is counted and propagates into the sums it enters.  16-byte loads and
+ * stores of the fp32 planes and 4-byte loads of the class maps when HW % 4 == 0, every fp32 tensor is 16-byte and both class maps
+ * are 4-byte aligned; scalar accesses otherwise (the two forms add in different orders: keep the bases aligned for rows that are
+ * a function of HW alone; the planes are the same bits either way).  ws: fp64 workspace of mau_raw_tile_ws_elems(B, HW) elements,
+ * tickets: a ZEROED mau_reduce_tickets_elems() buffer (left zeroed; see mau_reduce_rows_f64) -- both needed for rows only.  One
+ * launch per mau_reduce_tickets_elems() samples.  Refused (MAU_ERR_ARG): a NULL input, rows without ws / tickets, cont without
+ * targets or either without norm, nothing asked for, B <= 0, HW <= 0, HW > 2^30, num_classes outside [1,16], an fp32 tensor not
+ * 4-byte or an fp64 tensor not 8-byte aligned. */
+int mau_raw_tile_row_elems(void);
+size_t mau_raw_tile_ws_elems(int B, int64_t HW);
+int mau_raw_tile_process(const unsigned char* dw_t1, const unsigned char* dw_t2, const float* rgb, const float* ndvi_t1,
+                         const float* ndvi_t2, const float* temp_t1, const float* temp_t2, const double* norm, double* rows, float* cont,
+                         float* targets, double* ws, unsigned* tickets, int B, int64_t HW, int num_classes, mau_stream_t stream);
+
 /* ---- loss: F.mse_loss (src/utils/losses.py:27-39) -------------------------- */
 /* loss[0] = mean((out-tgt)^2) (fp64 accumulation, fixed order); dout (optional) = 2*(out-tgt)/n;
  * partial: fp64 workspace of mau_mse_blocks(n) elements. */

@@ -138,6 +138,9 @@ PROTOTYPES = {
     "mau_tile_stats_row_elems": (_i, []),
     "mau_tile_stats_ws_elems": (_sz, [_i, _i64]),
     "mau_tile_stats": (_i, [_p, _p, _p, _p, _p, _p, _p, _i, _i64, _i, _p]),
+    "mau_raw_tile_row_elems": (_i, []),
+    "mau_raw_tile_ws_elems": (_sz, [_i, _i64]),
+    "mau_raw_tile_process": (_i, [_p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _i, _i64, _i, _p]),
     "mau_mse_blocks": (_i, [_i64]),
     "mau_l1_gradient_blocks": (_i, [_i64]),
     "mau_l1_gradient_loss": (_i, [_p, _p, _p, _p, _p, _f, _f, _i, _i, _i, _i, _p]),
