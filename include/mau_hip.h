@@ -511,6 +511,36 @@ int mau_scenario_result(const float* out, const float* temp_orig, const unsigned
                         double temp_std, float* ndvi, float* temp_c, float* delta, double* rows, double* ws, unsigned* tickets, int N,
                         int H, int W, mau_stream_t stream);
 
+/* ---- region forecasts: a raster larger than one tile as overlapping windows at the trained resolution (the reference resizes the
+ *      whole region to one tile instead, app/gee_utils.py:40-87, app/processing_utils.py:122-128), ONE launch each.  Additive to ABI 5 ----
+ * mau_region_gather builds B window inputs from ONE resident region:
+ *   dw_t1, dw_t2 (Hr,Wr) uint8 class ids; rgb (3,Hr,Wr) fp32, raw 0..255; ndvi (Hr,Wr) fp32; temp (Hr,Wr) fp32, raw degrees C;
+ *   origins (B,2) int32 ON THE DEVICE, rows of (y0, x0): a captured graph is replayed for the next batch after a device-to-device
+ *   copy of B rows, no host synchronisation.  An origin is clamped to [0, Hr - T] x [0, Wr - T]: no index can leave the region;
+ *   norm: 8 fp64 on the device, mau_scenario_pack's layout.
+ *   out (B,T,T,ldo) in `dtype`, ldo % 8 == 0, ldo >= 2 ncls + 5 (MAU_ERR_ARG otherwise), 16-byte aligned:
+ *     [one-hot dw_t1 (ncls) | rgb (3) | ndvi | temp | one-hot dw_t2 (ncls) | zeros up to ldo]
+ *   with mau_scenario_pack's arithmetic exactly (one copy of the per-pixel code): fp64 normalisation with IEEE division rounded to
+ *   float once, NDVI bits passed through, the cast to `dtype` and a class id >= ncls (no channel set) as mau_pack_tile_onehot.
+ * MAU_ERR_ARG: T > min(Hr, Wr), T > 4096, ncls outside [1, mau_scenario_max_classes()], a bad ldo, B > 65535, Hr * Wr > 2^30. */
+int mau_region_gather(const unsigned char* dw_t1, const unsigned char* dw_t2, const float* rgb, const float* ndvi, const float* temp,
+                      const int* origins, const double* norm, void* out, int ldo, int dtype, int B, int T, int Hr, int Wr, int ncls,
+                      mau_stream_t stream);
+/* mau_region_stitch blends the windows' outputs into the region; pixel-owned, no atomics.
+ *   win (ny * nx, C, T, T) fp32, window k = iy * nx + ix at origin (ys[iy], xs[ix]); ys (ny), xs (nx) int32 on the device; ramp >= 1;
+ *   out (C,Hr,Wr) fp32.
+ * Integer weights w1(i) = min(i + 1, T - i, ramp), w = w1(y - y0) * w1(x - x0).  For a region pixel, over the windows that cover it,
+ * iy ascending and then ix ascending: num += (double)w * (double)v (every product exact in fp64), den += w (integer),
+ * out = (float)(num / (double)den), fp64 without contraction.  A pixel no window covers gets NaN; a pixel under one window gets that
+ * window's value bit for bit; the bits depend on neither the store width (16 bytes when Wr % 4 == 0 and out is 16-byte aligned, 4
+ * bytes otherwise) nor on how the windows were batched through the network.
+ * The tables are the caller's to check (the device cannot): strictly ascending, from 0 to Hr - T / Wr - T, no gap wider than T and at
+ * most THREE windows over any coordinate (the three table entries from the first window that reaches a pixel are examined).  For
+ * any other table the result is unspecified, but every access stays inside the four buffers.
+ * MAU_ERR_ARG: T > min(Hr, Wr), T > 4096, ramp < 1, Hr > 65535, Hr * Wr > 2^30, ny * nx > 2^20. */
+int mau_region_stitch(const float* win, const int* ys, const int* xs, float* out, int C, int T, int ramp, int Hr, int Wr, int ny, int nx,
+                      mau_stream_t stream);
+
 /* ---- model comparison: M heads' outputs of ONE tile against one target (the developer app's Model Comparison page,
  *      app_dev/pages/1_Model_Comparison.py with app_dev/app_src/utils.py:170-271), ONE launch each.  Additive to ABI 5 ----
  * mau_compare_result: out (M,2,H,W) fp32 NCHW, the M heads' outputs (channel 0 NDVI, channel 1 normalised temperature);

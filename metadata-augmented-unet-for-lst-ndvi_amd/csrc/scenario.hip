@@ -8,7 +8,8 @@
 // destination column); a painted pixel (alpha > 0) takes the palette entry of smallest squared RGB distance, the lowest index on
 // a tie -- integer arithmetic, which is what cdist + argmin give (the squares are exact in fp64 and sqrt is monotone).  The five
 // continuous planes are normalised in fp64 with IEEE division and rounded to float once: the bits of the reference's float64
-// numpy followed by .float().  A table entry outside the canvas is clamped (no read outside the buffer).
+// numpy followed by .float() (scn_pixel.h, shared with region_gather_kernel).  A table entry outside the canvas is clamped (no
+// read outside the buffer).
 //
 // result: a workgroup owns CHUNK_PIX consecutive pixels of ONE scenario -- the chunking is a function of H * W alone.  The
 // temperature is two separately rounded fp32 operations (numpy on a float32 array with Python-float scalars).  Sums are fp64 in
@@ -17,13 +18,12 @@
 // bits depend on nothing but its own scenario.
 #include <math.h>
 #include "chunk_reduce.h"
+#include "scn_pixel.h"
 
 #pragma clang fp contract(off)
 
 namespace mau {
 
-constexpr int SCN_MAX_CLS = 16;
-constexpr int SCN_NCONT = 5;             // rgb (3) + ndvi + temperature
 constexpr int SCN_ROW = 5;               // mean, min, max of the difference, edited pixels, mean of the difference over them
 // per-thread accumulators: 0 sum d  1 min d  2 max d  3 edited pixels  4 sum d over edited pixels
 constexpr int SCN_NV = 5;
@@ -58,26 +58,8 @@ __global__ __launch_bounds__(256) void scenario_pack_kernel(const uint8_t* __res
   }
   dw_t2[n * hw + ps] = (uint8_t)b;
   float cv[SCN_NCONT];
-#pragma unroll
-  for (int j = 0; j < 3; ++j) cv[j] = (float)(((double)rgb[j * hw + ps] / 255.0 - norm[j]) / norm[3 + j]);
-  cv[3] = ndvi[ps];
-  cv[4] = (float)(((double)temp[ps] - norm[6]) / norm[7]);
-  T* o = out + (n * hw + ps) * ld;
-  for (int g = 0; g < ld; g += 8) {
-    F8 v;
-#pragma unroll
-    for (int j = 0; j < 8; ++j) {
-      const int c = g + j;
-      float f = 0.f;
-      if (c < nc) f = (a == c) ? 1.f : 0.f;
-      else if (c < nc + SCN_NCONT) {
-        const int k = c - nc;
-        f = k == 0 ? cv[0] : k == 1 ? cv[1] : k == 2 ? cv[2] : k == 3 ? cv[3] : cv[4];
-      } else if (c < 2 * nc + SCN_NCONT) f = (b == c - nc - SCN_NCONT) ? 1.f : 0.f;
-      v.v[j] = f;
-    }
-    store8<T>(o + g, v);
-  }
+  scn_norm_planes(rgb, ndvi, temp, norm, hw, ps, cv);
+  scn_store_pixel<T>(out + (n * hw + ps) * ld, ld, nc, a, b, cv);
 }
 
 struct ScnJoin {
