@@ -470,6 +470,47 @@ size_t mau_eval_metrics_ws_elems(int B, int C, int H, int W, int ncls);
 int mau_eval_metrics(const float* out, const float* tgt, const unsigned char* cls, const double* scale, const double* shift,
                      double* rows, double* ws, unsigned* tickets, int B, int C, int H, int W, int ncls, mau_stream_t stream);
 
+/* ---- statistical comparison of M checkpoints (test/statistical_tests.py, the numbers of app_dev/pages/3_Statistical_Comparison.py):
+ *      the M models' metric rows in ONE launch, their joint moments per group in ONE more.  Additive to ABI 5 ----
+ * mau_eval_metrics_multi: out (M,B,C,H,W) fp32, the M models' outputs; tgt, cls, scale, shift, ncls, tickets as mau_eval_metrics;
+ * M in [1, mau_eval_metrics_multi_max_models() = 8] (MAU_ERR_ARG otherwise), every other argument by mau_eval_metrics's rules.
+ *   rows: (M, B*C, mau_eval_metrics_row_elems(ncls)) fp64; row [m][b*C + c] has EXACTLY the bits mau_eval_metrics gives for out[m],
+ *   tgt, cls: the same chunking, per-thread pixel order and joins.  A row does not depend on M or on the model's place.
+ * A workgroup owns one chunk of one (sample, channel) and walks the M models over it: the chunk's un-normalised target values,
+ * their Laplacians and the class ids are formed once and kept in registers, and what depends on the target alone ([3], [5], [8],
+ * [9], [10] and the class counts) is joined once and written into every model's row -- 4 M + 5 bytes per pixel and channel instead
+ * of 9 M.  (A map wider than 4096 pixels has more than 16 pixels per thread: its target values are formed again per model.)
+ * ws: fp64 workspace of mau_eval_metrics_multi_ws_elems(M, B, C, H, W, ncls) elements; tickets: a ZEROED
+ * mau_reduce_tickets_elems() buffer (left zeroed).  One launch per mau_reduce_tickets_elems() rows. */
+int mau_eval_metrics_multi_max_models(void);
+size_t mau_eval_metrics_multi_ws_elems(int M, int B, int C, int H, int W, int ncls);
+int mau_eval_metrics_multi(const float* out, const float* tgt, const unsigned char* cls, const double* scale, const double* shift,
+                           double* rows, double* ws, unsigned* tickets, int M, int B, int C, int H, int W, int ncls,
+                           mau_stream_t stream);
+/* mau_paired_accumulate: merges the samples of a batch into table [G][C][4 + 2 ncls] of entries (DEVICE resident, zeroed by the caller
+ * before the first batch), G = mau_paired_groups() = 8 = 4 * is_known_city + temporal distance (0 long: t1_year <= 2021, 1 mid:
+ * 2022-2023, 2 short: > 2023, 3 other; statistical_tests.py:12-20).
+ *   rows: (M, B*C, mau_eval_metrics_row_elems(ncls)) fp64, as mau_eval_metrics_multi writes them; M in [1,8], ncls in [1,16];
+ *   group: (B) uint8 on the device, the sample's group; an id >= G drops the sample.
+ * Slot s of (group, channel): s < 4 the overall metrics, row entries [0] mae, [1] rmse, [2] laplacian_var_pred, [3]
+ * laplacian_var_gt; s = 4 + 2 k + w the class k's mae (w = 0, row entry [11 + ncls + k]) or rmse (w = 1, [11 + 2 ncls + k]).
+ * x = the M-vector of that row entry in the M models' rows of the sample.  A sample enters a class slot only if the class has pixels
+ * in it (row entry [11 + k] > 0; the models share the class map); a sample with a non-finite x_i for any i is counted and left out
+ * for all models.
+ * An entry is mau_paired_entry_elems(M) = 2 + M + M (M + 1) / 2 fp64:
+ *   [0] n, the samples that entered   [1] the samples skipped for a non-finite value   [2 + i] mean_i
+ *   [2 + M + p] Cm_ij = sum (x_i - mean_i)(x_j - mean_j), the upper triangle row-major, p = 0, 1, ... over i <= j.
+ * Update per entering sample, in sample order, fp64, not contracted:
+ *   n' = n + 1;  d_i = x_i - mean_i;  mean_i' = mean_i + d_i / n';  Cm_ij' = Cm_ij + d_i * (x_j - mean_j').
+ * One thread per entry, no atomics, no tickets: the table after any sequence of batches has the bits of the table after the same
+ * samples in one batch.  mau_paired_table_elems(M, C, ncls) = G * C * (4 + 2 ncls) * mau_paired_entry_elems(M); the size queries
+ * return 0 for arguments the call refuses. */
+int mau_paired_groups(void);
+int mau_paired_entry_elems(int M);
+size_t mau_paired_table_elems(int M, int C, int ncls);
+int mau_paired_accumulate(const double* rows, const unsigned char* group, double* table, int M, int B, int C, int ncls,
+                          mau_stream_t stream);
+
 /* ---- scenario sessions: a painted canvas -> the network's input, the head's output -> temperature change (the app's per-click path,
  *      app/Home.py:333-411 with app/processing_utils.py:70-181), ONE launch each.  Additive to ABI 5 ----
  * mau_scenario_pack builds N scenario inputs from ONE base tile:

@@ -20,10 +20,11 @@ def __getattr__(name):
     # (test-split evaluation), ``mau_amd.scenario`` (scenario sessions of the app) and ``mau_amd.dataset_metrics`` (the dataset
     # survey) and ``mau_amd.compare`` (model comparison sessions) are also command lines, ``python -m mau_amd.sensitivity`` /
     # ``.ground_truth`` / ``.evaluate`` / ``.scenario`` / ``.dataset_metrics`` / ``.compare``, and so are ``mau_amd.dataset_build`` (raw
-    # tiles -> the processed dataset) and ``mau_amd.region`` (region forecasts: windows gathered and blended on the device): they
-    # are imported on first use, so that running one as a script does not find it in sys.modules already
+    # tiles -> the processed dataset) and ``mau_amd.region`` (region forecasts: windows gathered and blended on the device) and
+    # ``mau_amd.statistics`` (paired tests of several checkpoints in one pass over the test split): they are imported on first use,
+    # so that running one as a script does not find it in sys.modules already
     import importlib
-    if name in ("sensitivity", "ground_truth", "evaluate", "scenario", "dataset_metrics", "compare", "dataset_build", "region"):
+    if name in ("sensitivity", "ground_truth", "evaluate", "scenario", "dataset_metrics", "compare", "dataset_build", "region", "statistics"):
         return importlib.import_module("." + name, __name__)
     if name in ("ScenarioSession", "ScenarioResult"):
         return getattr(importlib.import_module(".scenario", __name__), name)
@@ -38,4 +39,4 @@ __all__ = ["UrbanPredictor", "UrbanPredictor_unet", "UrbanPredictor_unetpp", "VG
            "TemporalEncoder", "compute_loss_mse", "compute_loss_mse_gradient", "compute_loss_l1_grad_ssim", "compute_all_loss", "gradient_loss",
            "GraphedInference", "GraphedTrainStep", "AdamW", "Adam", "SGD", "mark_params_updated", "sensitivity", "ground_truth", "evaluate", "scenario",
            "dataset_metrics", "ScenarioSession", "ScenarioResult", "compare", "ComparisonSession", "ComparisonResult", "dataset_build",
-           "region", "RegionSession", "RegionResult"]
+           "region", "RegionSession", "RegionResult", "statistics"]

@@ -118,6 +118,13 @@ PROTOTYPES = {
     "mau_eval_metrics_chunks": (_i, [_i, _i]),
     "mau_eval_metrics_ws_elems": (_sz, [_i, _i, _i, _i, _i]),
     "mau_eval_metrics": (_i, [_p, _p, _p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _p]),
+    "mau_eval_metrics_multi_max_models": (_i, []),
+    "mau_eval_metrics_multi_ws_elems": (_sz, [_i, _i, _i, _i, _i, _i]),
+    "mau_eval_metrics_multi": (_i, [_p, _p, _p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _i, _p]),
+    "mau_paired_groups": (_i, []),
+    "mau_paired_entry_elems": (_i, [_i]),
+    "mau_paired_table_elems": (_sz, [_i, _i, _i]),
+    "mau_paired_accumulate": (_i, [_p, _p, _p, _i, _i, _i, _i, _p]),
     "mau_scenario_max_classes": (_i, []),
     "mau_scenario_pack": (_i, [_p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _i, _p, _i, _i, _i, _i, _i, _i, _i, _p]),
     "mau_scenario_result_row_elems": (_i, []),

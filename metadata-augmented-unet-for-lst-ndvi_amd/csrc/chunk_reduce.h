@@ -1,4 +1,4 @@
-// chunk_reduce.h -- the two-level fixed-order fp64 reduction of the analysis kernels (evalmetrics.hip, scenario.hip, gtstats.hip,
+// chunk_reduce.h -- the two-level fixed-order fp64 reduction of the analysis kernels (evalmetrics.hip, evalmulti.hip, scenario.hip, gtstats.hip,
 // tilestats.hip, compare.hip, loss_terms.hip; the launch loop also head.hip's mau_head_mean), written once.
 //
 // A row (a plane, a scenario, a sample) is cut into chunks of CHUNK_PIX consecutive pixels, one 256-thread workgroup each -- the

@@ -12,28 +12,11 @@
 // The class sums are kept in registers: bin k takes `cls == k ? value : 0`, one select per bin and pixel, so that no
 // accumulator is indexed dynamically (fp64 rate is not what limits a kernel that reads 9 bytes per pixel).
 #include <math.h>
-#include "chunk_reduce.h"
+#include "eval_row.h"
 
 #pragma clang fp contract(off)
 
 namespace mau {
-
-constexpr int EVAL_MAX_CLS = 16;
-constexpr int EVAL_HEAD = 11;            // row entries in front of the per-class blocks (include/mau_hip.h)
-// per-thread accumulators: 0 sum|d| 1 sum d^2 2,3 sum / sum of squares of lap(p) 4,5 of lap(g) 6,7 non-finite out / tgt
-// 8 min p 9 max p 10 min g 11 max g, then NB counts, NB sums |d|, NB sums d^2 (bin NB-1: class ids >= ncls)
-constexpr int EVAL_ACC0 = 12;
-
-// image rows of a workgroup: a run of at most CHUNK_PIX pixels (250 x 250: 16 rows, 16 chunks per map)
-static inline int eval_rows_per_chunk(int W) { return W >= CHUNK_PIX ? 1 : CHUNK_PIX / W; }
-static inline int eval_chunks(int H, int W) { return ceil_div(H, eval_rows_per_chunk(W)); }
-static inline int eval_bins(int ncls) { return ncls <= 9 ? 10 : EVAL_MAX_CLS + 1; }
-
-struct EvalJoin {
-  __device__ __forceinline__ double operator()(int v, double a, double b) const {
-    return (v == 8 || v == 10) ? fmin(a, b) : (v == 9 || v == 11) ? fmax(a, b) : a + b;
-  }
-};
 
 template <int NB>
 __global__ __launch_bounds__(256) void eval_metrics_kernel(const float* __restrict__ out, const float* __restrict__ tgt,
@@ -62,16 +45,12 @@ __global__ __launch_bounds__(256) void eval_metrics_kernel(const float* __restri
   acc[9] = acc[11] = -INFINITY;
 
   for (int idx = threadIdx.x; idx < npx; idx += 256) {
-    const int di = idx / W;
-    const int i = i0 + di, j = idx - di * W;
-    const size_t q = (size_t)i * W + j;
-    // the four neighbours with the edge sample repeated (an axis of one pixel contributes x + x - 2x)
-    const size_t qu = i > 0 ? q - W : q, qd = i + 1 < H ? q + W : q;
-    const size_t ql = j > 0 ? q - 1 : q, qr = j + 1 < W ? q + 1 : q;
-    const float of = o[q], tf = t[q];
-    const double p = (double)of * sc + sh, g = (double)tf * sc + sh;
-    const double lp = ((((double)o[qu] * sc + sh) + ((double)o[qd] * sc + sh)) + ((double)o[ql] * sc + sh)) + ((double)o[qr] * sc + sh) - 4.0 * p;
-    const double lg = ((((double)t[qu] * sc + sh) + ((double)t[qd] * sc + sh)) + ((double)t[ql] * sc + sh)) + ((double)t[qr] * sc + sh) - 4.0 * g;
+    const EvalStencil s = eval_stencil(idx, i0, H, W);
+    const size_t q = s.q;
+    float of, tf;
+    double p, lp, g, lg;
+    eval_value_lap(o, s, sc, sh, of, p, lp);
+    eval_value_lap(t, s, sc, sh, tf, g, lg);
     const double d = p - g;
     const double a = fabs(d), d2 = d * d;
     acc[0] += a;
@@ -108,28 +87,7 @@ __global__ __launch_bounds__(256) void eval_metrics_kernel(const float* __restri
   double* r = rows + (size_t)row * relems;
   const double n = (double)HW;
   const int e = threadIdx.x;
-  if (e < relems) {
-    double val;
-    if (e == 0) {
-      val = tot[0] / n;
-    } else if (e == 1) {
-      val = sqrt(tot[1] / n);
-    } else if (e == 2 || e == 3) {           // population variance from the two sums; never below zero
-      const double m = tot[2 * e - 2] / n;
-      val = tot[2 * e - 1] / n - m * m;
-      val = val < 0.0 ? 0.0 : val;
-    } else if (e < 10) {
-      val = tot[e + 2];
-    } else if (e == 10) {
-      val = tot[EVAL_ACC0 + NB - 1];
-    } else {
-      const int blk = (e - EVAL_HEAD) / ncls, kk = (e - EVAL_HEAD) - blk * ncls;
-      const double cnt = tot[EVAL_ACC0 + kk];
-      // an absent class: 0 / 0 = NaN, the host turns it into "no row"
-      val = blk == 0 ? cnt : blk == 1 ? tot[EVAL_ACC0 + NB + kk] / cnt : sqrt(tot[EVAL_ACC0 + 2 * NB + kk] / cnt);
-    }
-    r[e] = val;
-  }
+  if (e < relems) r[e] = eval_row_entry<NB>(tot, e, ncls, n);
 }
 
 }  // namespace mau
