@@ -63,16 +63,35 @@ def resolve_embedding_flags(checkpoint: Dict[str, Any], study_name: str = "") ->
     return False, False
 
 
+# (temporal_dim, meta_dim, lstm_hidden) of a checkpoint whose hyperparameters do not name them: the reference's readers disagree
+EVAL_WIDTHS = (64, 64, 96)                  # the app's and the evaluation's reader (app/model_utils.py:66-88, test/evaluate.py:152-164)
+SENSITIVITY_WIDTHS = (16, 8, 32)            # the sensitivity script's (test/metadata_sensitivity.py:79-133)
+
+
 def model_kwargs_from_checkpoint(checkpoint: Dict[str, Any], spatial_channels: int = 23, seq_len: int = 10,
-                                 out_channels: int = 2, study_name: str = "") -> Dict[str, Any]:
+                                 out_channels: int = 2, study_name: str = "", widths=EVAL_WIDTHS) -> Dict[str, Any]:
     """Constructor arguments as the reference's readers derive them (app/model_utils.py:66-88;
     test/evaluate.py:152-164 uses CONFIG for spatial_channels / seq_len)."""
     hyper = checkpoint.get("hyperparameters", {})
     t_emb, m_emb = resolve_embedding_flags(checkpoint, study_name)
     return dict(model_type=checkpoint.get("model_type", "unet"), spatial_channels=spatial_channels, seq_len=seq_len,
-                temporal_dim=hyper.get("temporal_dim", 64), meta_features=checkpoint.get("metadata_input_length", 4),
-                meta_dim=hyper.get("meta_dim", 64), lstm_dim=hyper.get("lstm_hidden", 96), out_channels=out_channels,
+                temporal_dim=hyper.get("temporal_dim", widths[0]), meta_features=checkpoint.get("metadata_input_length", 4),
+                meta_dim=hyper.get("meta_dim", widths[1]), lstm_dim=hyper.get("lstm_hidden", widths[2]), out_channels=out_channels,
                 temporal_embeddings=t_emb, metadata_embeddings=m_emb)
+
+
+def load_reference_checkpoint(checkpoint_path: str, seq_len: int, widths, study_name: str = "", device: str = "cuda"):
+    """(eval-mode model on ``device``, checkpoint dict) of a reference-layout checkpoint: input channels, filter width and output
+    channels are read off the state dict, the rest is ``model_kwargs_from_checkpoint``'s with the fallback ``widths`` of the
+    reader that is mirrored (``EVAL_WIDTHS`` or ``SENSITIVITY_WIDTHS``)."""
+    ckpt = torch.load(checkpoint_path, map_location="cpu", weights_only=False)
+    sd = ckpt["model_state_dict"]
+    w0 = sd["model.conv0_0.conv1.weight"]
+    kw = model_kwargs_from_checkpoint(ckpt, spatial_channels=w0.shape[1], seq_len=seq_len, out_channels=sd["model.final.weight"].shape[0],
+                                      study_name=study_name, widths=widths)
+    model = UrbanPredictor(base_filters=w0.shape[0], **kw)
+    model.load_state_dict(sd)
+    return model.to(device).eval(), ckpt
 
 
 def load_model(model_path: str, device: str = "cuda", spatial_channels: int = 23, seq_len: int = 10, out_channels: int = 2,

@@ -29,7 +29,9 @@ import numpy as np
 import torch
 
 from . import functional as F_
-from .functional import call, lib
+from ._capture import freeze, warm_up_and_capture
+from .functional import _dev, call, lib
+from .scenario import _check_metrics, _norm_row, _palette, palette_from_hex
 
 N_CONT = 5               # rgb (3) + ndvi + temperature
 REGIONS = ("tile", "top_left", "top_right", "bottom_left", "bottom_right")
@@ -45,19 +47,6 @@ SAMPLE_KEYS = ("cls_a", "cls_b", "cont", "metadata", "temp_series", "t1_date", "
 def quadrants(H: int, W: int) -> Tuple[Tuple[int, int, int, int], ...]:
     """(y1, y2, x1, x2) of top-left, top-right, bottom-left, bottom-right (utils.py:173-178)."""
     return ((0, H // 2, 0, W // 2), (0, H // 2, W // 2, W), (H // 2, H, 0, W // 2), (H // 2, H, W // 2, W))
-
-
-def _check_metrics(metrics: dict, keys):
-    missing = [k for k in keys if k not in metrics]
-    if missing:
-        raise ValueError(f"metrics lacks {missing} (the keys of normalization_metrics.json)")
-
-
-def _palette(palette) -> np.ndarray:
-    p = np.asarray(palette)
-    if p.ndim != 2 or p.shape[1] != 3 or p.dtype != np.uint8 or p.shape[0] < 1:
-        raise ValueError("palette must be an (ncls, 3) uint8 array, ncls >= 1")
-    return np.ascontiguousarray(p)
 
 
 def _region_entries(g: np.ndarray, p: np.ndarray, e: np.ndarray) -> np.ndarray:
@@ -198,17 +187,6 @@ class InputViews(NamedTuple):
     dw_t2_rgb: torch.Tensor     # (H, W, 3) uint8
 
 
-def _dev(t, what: str, dtype, shape=None) -> torch.Tensor:
-    if not isinstance(t, torch.Tensor):
-        raise TypeError(f"{what} must be a torch tensor on the device, got {type(t).__name__}")
-    F_._require_cuda(t, what)
-    if t.dtype != dtype:
-        raise TypeError(f"{what} must be {dtype}, got {t.dtype}")
-    if shape is not None and tuple(t.shape) != tuple(shape):
-        raise ValueError(f"{what} must be {tuple(shape)}, got {tuple(t.shape)}")
-    return t.detach().contiguous()
-
-
 def result(outputs: torch.Tensor, target: torch.Tensor, temp_mean: float, temp_std: float,
            tickets: Optional[torch.Tensor] = None) -> ComparisonResult:
     """One launch (``mau_compare_result``) per ``mau_reduce_tickets_elems()`` rows: the M heads' outputs (M, 2, H, W) fp32 and
@@ -233,16 +211,13 @@ class _ViewTables:
     """The device-side constants of ``mau_compare_inputs`` for one (palette, metrics)."""
 
     def __init__(self, palette, metrics: dict, dev):
-        _check_metrics(metrics, ("rgb_mean", "rgb_std", "temp_mean", "temp_std"))
+        _check_metrics(metrics)
         palette = _palette(palette)
         self.ncls = palette.shape[0]
         if self.ncls > lib.mau_scenario_max_classes():
             raise ValueError(f"mau_compare_inputs takes at most {lib.mau_scenario_max_classes()} classes, the palette has {self.ncls}")
-        norm = np.array(list(metrics["rgb_mean"]) + list(metrics["rgb_std"]) + [metrics["temp_mean"], metrics["temp_std"]], dtype=np.float64)
-        if norm.shape != (8,):
-            raise ValueError("metrics: rgb_mean and rgb_std hold three values each")
         self.palette = torch.from_numpy(palette).to(dev)
-        self.norm = torch.from_numpy(norm).to(dev)
+        self.norm = torch.from_numpy(_norm_row(metrics)).to(dev)
 
 
 def _input_views(cls_a, cls_b, cont, tb: _ViewTables, out: Optional[InputViews] = None) -> InputViews:
@@ -308,16 +283,16 @@ class ComparisonSession:
             raise ValueError("ComparisonSession: at least one model")
         _check_metrics(metrics, ("temp_mean", "temp_std"))
         self.names = [str(name) for name, _ in models]
-        self.models = [model.eval() for _, model in models]
+        self.models = [model for _, model in models]
         self.clone_output = clone_output
         self.num_classes = int(num_classes if num_classes is not None else NUM_CLASSES)
         dev = next(self.models[0].parameters()).device
+        dtypes = set()
         for name, model in zip(self.names, self.models):
             F_._require_cuda(next(model.parameters()), f"ComparisonSession(model {name!r})")
             if precision is not None:
                 model.set_precision(precision)
-            model.freeze_inference(True)
-        dtypes = {getattr(m, "model", m)._rt.dtype for m in self.models}
+            dtypes.add(freeze(model))
         if len(dtypes) != 1:
             raise ValueError(f"ComparisonSession: the models compute in {sorted(str(d) for d in dtypes)}; the tile is packed once, "
                              "pass precision= or set one precision on all of them")
@@ -335,15 +310,7 @@ class ComparisonSession:
         self.views = None if self._tables is None else _input_views(self._buf["cls_a"][0], self._buf["cls_b"][0], self._buf["cont"][0], self._tables)
         # the tickets of the captured reduction are the session's own: a replay never shares them with a launch on another stream
         self._tickets = torch.zeros(lib.mau_reduce_tickets_elems(), dtype=torch.int32, device=dev)
-        side = torch.cuda.Stream(device=dev)
-        side.wait_stream(torch.cuda.current_stream())
-        with torch.cuda.stream(side), torch.no_grad():
-            for _ in range(max(1, warmup)):            # packs weights, sets kernel attributes, warms the allocator
-                self._run()
-        torch.cuda.current_stream().wait_stream(side)
-        self.graph = torch.cuda.CUDAGraph()
-        with torch.no_grad(), torch.cuda.graph(self.graph):
-            self._out = self._run()
+        self.graph, self._out = warm_up_and_capture(self._run, dev, warmup)
         self._out.names, self._out.views = self.names, self.views
 
     @staticmethod
@@ -414,7 +381,6 @@ def compare_checkpoints(checkpoints: Sequence[str], processed_dir: str, *, split
     five input views; the returned dict also carries ``lines``, one per model and channel."""
     from .data import FuturePredictionDataset
     from .evaluate import load_for_evaluation
-    from .scenario import palette_from_hex
     if not checkpoints:
         raise ValueError("compare_checkpoints: at least one checkpoint")
     if (index is None) == (filename is None):
@@ -470,9 +436,7 @@ def main(argv=None) -> int:
     p.add_argument("--output", default="", help=".npz to write pred, gt, err, stats, names and the input views to")
     p.add_argument("--device", default="gpu", help="'gpu' or a torch device name; this path has no CPU fallback")
     a = p.parse_args(argv)
-    device = "cuda:0" if a.device.lower() == "gpu" else a.device
-    if device.lower() == "cpu":
-        p.error("this is the MI355X-native path: --device gpu (there is no CPU fallback)")
+    device = F_.argparse_device(p, a.device)
     res = compare_checkpoints(a.checkpoints, a.processed_dir, split=a.split, index=a.index, filename=a.filename, metrics_json=a.metrics_json,
                               palette_json=a.palette_json, precision=a.precision, output=a.output, device=device)
     for line in res["lines"]:

@@ -336,9 +336,8 @@ def main(argv: Optional[Sequence[str]] = None) -> int:
     e.add_argument("--num-workers", type=int, default=0)
     e.add_argument("--device", default="gpu", help="'gpu' or a torch device name; this path has no CPU fallback")
     a = p.parse_args(argv)
-    device = "cuda:0" if a.device.lower() == "gpu" else a.device
-    if device.lower() == "cpu":
-        p.error("this is the MI355X-native path: --device gpu (there is no CPU fallback)")
+    from .functional import argparse_device
+    device = argparse_device(p, a.device)
     try:
         extract(a.input_dir, a.output_csv, a.metrics_json, a.batch_size, a.num_workers, device)
     except FileNotFoundError as err:

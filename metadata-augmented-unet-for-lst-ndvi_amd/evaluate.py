@@ -105,29 +105,44 @@ def _coeffs(v, C: int, dev, what: str, default: float) -> torch.Tensor:
     return t.to(dev).contiguous()
 
 
+def _checked_args(fn: str, outputs, targets, cls, scale, shift, num_classes: int, max_models: int = 0):
+    """The argument check of ``eval_metrics`` and ``statistics.eval_metrics_multi`` (``fn``: the caller's name in the messages):
+    outputs, targets fp32 and cls uint8 on the device, targets (B, C, H, W), cls (B, H, W), outputs of targets' shape -- with
+    ``max_models`` behind a leading M in [1, max_models] --, ``num_classes`` in range, nothing empty.  Returns the three tensors
+    detached and contiguous and scale, shift as (C,) fp64 device tensors."""
+    for t, what in ((outputs, "outputs"), (targets, "targets"), (cls, "cls")):
+        F_._require_cuda(t, f"{fn}({what})")
+    if outputs.dtype != torch.float32 or targets.dtype != torch.float32:
+        raise TypeError(f"{fn}: outputs and targets must be float32, got {outputs.dtype} and {targets.dtype}")
+    if cls.dtype != torch.uint8:
+        raise TypeError(f"{fn}: cls must be uint8, got {cls.dtype}")
+    if max_models:
+        if outputs.dim() != 5 or targets.dim() != 4 or outputs.shape[1:] != targets.shape:
+            raise ValueError(f"{fn}: outputs must be (M, B, C, H, W) and targets (B, C, H, W), got {tuple(outputs.shape)} and {tuple(targets.shape)}")
+        if not 1 <= outputs.shape[0] <= max_models:
+            raise ValueError(f"{fn}: M must be in [1, {max_models}], got {outputs.shape[0]}")
+    elif outputs.dim() != 4 or outputs.shape != targets.shape:
+        raise ValueError(f"{fn}: outputs and targets must be (B, C, H, W) of one shape, got {tuple(outputs.shape)} and {tuple(targets.shape)}")
+    B, C, H, W = targets.shape
+    if tuple(cls.shape) != (B, H, W):
+        raise ValueError(f"{fn}: cls must be {(B, H, W)}, got {tuple(cls.shape)}")
+    if not 1 <= num_classes <= MAX_CLASSES:
+        raise ValueError(f"{fn}: num_classes must be in [1, {MAX_CLASSES}], got {num_classes}")
+    if B * C * H * W == 0:
+        raise ValueError(f"{fn}: empty batch")
+    dev = outputs.device
+    return (outputs.detach().contiguous(), targets.detach().contiguous(), cls.contiguous(),
+            _coeffs(scale, C, dev, "scale", 1.0), _coeffs(shift, C, dev, "shift", 0.0))
+
+
 def eval_metrics(outputs: torch.Tensor, targets: torch.Tensor, cls: torch.Tensor, scale=None, shift=None,
                  num_classes: int = len(DW_CLASS_NAMES)) -> EvalMetrics:
     """Per (sample, channel) metrics of ``outputs * scale + shift`` against ``targets * scale + shift`` in one launch.
     outputs, targets (B, C, H, W) fp32 on the device; cls (B, H, W) uint8; scale / shift: one value per channel (None = 1 / 0).
     A row depends on its own maps only: not on B, not on the sample's position; repeated calls agree bit for bit."""
-    for t, what in ((outputs, "outputs"), (targets, "targets"), (cls, "cls")):
-        F_._require_cuda(t, f"eval_metrics({what})")
-    if outputs.dtype != torch.float32 or targets.dtype != torch.float32:
-        raise TypeError(f"eval_metrics: outputs and targets must be float32, got {outputs.dtype} and {targets.dtype}")
-    if cls.dtype != torch.uint8:
-        raise TypeError(f"eval_metrics: cls must be uint8, got {cls.dtype}")
-    if outputs.dim() != 4 or outputs.shape != targets.shape:
-        raise ValueError(f"eval_metrics: outputs and targets must be (B, C, H, W) of one shape, got {tuple(outputs.shape)} and {tuple(targets.shape)}")
-    B, C, H, W = outputs.shape
-    if tuple(cls.shape) != (B, H, W):
-        raise ValueError(f"eval_metrics: cls must be {(B, H, W)}, got {tuple(cls.shape)}")
-    if not 1 <= num_classes <= MAX_CLASSES:
-        raise ValueError(f"eval_metrics: num_classes must be in [1, {MAX_CLASSES}], got {num_classes}")
-    if B * C * H * W == 0:
-        raise ValueError("eval_metrics: empty batch")
+    outputs, targets, cls, scale, shift = _checked_args("eval_metrics", outputs, targets, cls, scale, shift, num_classes)
+    B, C, H, W = targets.shape
     dev = outputs.device
-    outputs, targets, cls = outputs.detach().contiguous(), targets.detach().contiguous(), cls.contiguous()
-    scale, shift = _coeffs(scale, C, dev, "scale", 1.0), _coeffs(shift, C, dev, "shift", 0.0)
     rows = torch.empty((B, C, lib.mau_eval_metrics_row_elems(num_classes)), dtype=torch.float64, device=dev)
     ws = torch.empty(lib.mau_eval_metrics_ws_elems(B, C, H, W, num_classes), dtype=torch.float64, device=dev)
     call("mau_eval_metrics", outputs.data_ptr(), targets.data_ptr(), cls.data_ptr(), scale.data_ptr(), shift.data_ptr(),
@@ -238,19 +253,89 @@ def load_for_evaluation(checkpoint_path: str, study_name: str = "", device: str 
     """(eval-mode model, checkpoint dict) of a reference-layout checkpoint: ``checkpoint.model_kwargs_from_checkpoint``'s
     rules (embedding flags, ``metadata_input_length``), the config's ``temporal_length`` and target channels as
     test/evaluate.py:152-164; input channels and filter width are read off the first convolution's weight."""
-    from .checkpoint import model_kwargs_from_checkpoint
+    from .checkpoint import EVAL_WIDTHS, load_reference_checkpoint
     from .config import CONFIG
-    from .model import UrbanPredictor
     if not os.path.exists(checkpoint_path):
         raise FileNotFoundError(f"Checkpoint not found at: {checkpoint_path}")
-    ckpt = torch.load(checkpoint_path, map_location="cpu", weights_only=False)
-    sd = ckpt["model_state_dict"]
-    w0 = sd["model.conv0_0.conv1.weight"]
-    kw = model_kwargs_from_checkpoint(ckpt, spatial_channels=w0.shape[1], seq_len=CONFIG.dataset.temporal_length,
-                                      out_channels=sd["model.final.weight"].shape[0], study_name=study_name)
-    model = UrbanPredictor(base_filters=w0.shape[0], **kw)
-    model.load_state_dict(sd)
-    return model.to(device).eval(), ckpt
+    return load_reference_checkpoint(checkpoint_path, CONFIG.dataset.temporal_length, EVAL_WIDTHS, study_name, device)
+
+
+def temperature_coeffs(channels: Sequence[str], metrics: Optional[dict]):
+    """(scale, shift) per channel that un-normalise the temperature channels ("temp" in the name) with the metrics' ``temp_std`` and
+    ``temp_mean`` and leave the others -- NDVI -- as they are (get_unnormalized_data, test/evaluate.py:23-41); no metrics: raw values."""
+    scale = [float(metrics["temp_std"]) if metrics and "temp" in ch.lower() else 1.0 for ch in channels]
+    shift = [float(metrics["temp_mean"]) if metrics and "temp" in ch.lower() else 0.0 for ch in channels]
+    return scale, shift
+
+
+def open_test_split(checkpoint_paths: Sequence[str], processed_dir: str, *, batch_size: Optional[int], precision: Optional[str],
+                    study_name: str, metrics_json: Optional[str], device: str):
+    """What a walk over the ``test`` split of ``processed_dir`` needs, for one checkpoint or several: (models -- loaded, frozen --,
+    their checkpoint dicts, channel names, scale, shift, the train split's cities, the loader).  batch_size: default the first
+    checkpoint's ``hyperparameters.batch_size``, else 16.  ``metrics_json``: default ``<processed_dir>/normalization_metrics.json``
+    when it exists, else raw values (test/evaluate.py:169-174)."""
+    from .config import CONFIG
+    from .data import create_dataloader
+    models, ckpts = [], []
+    for path in checkpoint_paths:
+        model, ckpt = load_for_evaluation(path, study_name, device)
+        if precision is not None:
+            model.set_precision(precision)
+        model.eval().freeze_inference()
+        models.append(model)
+        ckpts.append(ckpt)
+    Co = models[0].model.final.weight.shape[0]
+    if any(m.model.final.weight.shape[0] != Co for m in models):
+        raise ValueError("compare_checkpoints: the checkpoints do not have the same number of output channels")
+    bs = int(batch_size if batch_size is not None else ckpts[0].get("hyperparameters", {}).get("batch_size", 16))
+    channels = list(CONFIG.dataset.target_channels)
+    if len(channels) != Co:
+        channels = [f"channel_{i}" for i in range(Co)]
+    if metrics_json is None:
+        default = os.path.join(processed_dir, "normalization_metrics.json")
+        metrics_json = default if os.path.exists(default) else ""
+    metrics = None
+    if metrics_json:
+        with open(metrics_json) as f:
+            metrics = json.load(f)
+    else:
+        log.warning("Normalization metrics not found. Using raw data.")
+    scale, shift = temperature_coeffs(channels, metrics)
+    known = train_cities(processed_dir)
+    # the plain loader: DeviceLoader's 7-tuple drops cls_a, which the metrics need
+    loader = create_dataloader("test", bs, False, processed_dir=processed_dir, device=None)
+    return models, ckpts, channels, scale, shift, known, loader
+
+
+def walk_test_split(loader, known: set, device: str):
+    """Per batch of the loader: (the host batch, the batch on the device, the index of its first sample, ``infos``) -- ``infos[i]``
+    holds the columns of sample i that are not metrics: is_known_city, the dates, time_delta, and city, lat, lon."""
+    dataset = loader.dataset
+    sample_idx = 0
+    for host in loader:
+        batch = host.pin().to(device)
+        infos = []
+        for i in range(int(host.t1_dates.shape[0])):
+            t1y, t1m = int(host.t1_dates[i, 0]), int(host.t1_dates[i, 1])
+            t2y, t2m = int(host.t2_dates[i, 0]), int(host.t2_dates[i, 1])
+            info = dataset.get_metadata_from_idx(sample_idx + i)
+            infos.append({"is_known_city": info["city"] in known, "t1_year": t1y, "t1_month": t1m, "t2_year": t2y,
+                          "t2_month": t2m, "time_delta": t2y - t1y, **info})
+        yield host, batch, sample_idx, infos
+        sample_idx += len(infos)
+
+
+def network_inputs(batch, model, ckpt: dict, packed: dict):
+    """(inputs, temp_series, metadata, targets) of one model for a device batch.  ``packed`` caches the packed batch per network
+    dtype (one dict per batch); a checkpoint with ``metadata_input_length`` 8 gets the two dates appended to the metadata."""
+    from .data import to_network_inputs
+    dtype = model.model._rt.dtype
+    if dtype not in packed:
+        packed[dtype] = to_network_inputs(batch, dtype)
+    inputs, metadata, temp_series, _lengths, t1_dates, t2_dates, targets = packed[dtype]
+    if ckpt.get("metadata_input_length", 4) == 8:
+        metadata = torch.cat([metadata, t1_dates, t2_dates], dim=1)
+    return inputs, temp_series, metadata, targets
 
 
 @torch.no_grad()
@@ -261,60 +346,17 @@ def evaluate_checkpoint(checkpoint_path: str, processed_dir: str, *, batch_size:
     Returns {'rows', 'summary', 'report_path', 'info_path'}.  ``metrics_json``: the normalisation metrics (temp_mean,
     temp_std); default ``<processed_dir>/normalization_metrics.json`` when it exists, else raw values (:169-174)."""
     from .checkpoint import resolve_embedding_flags
-    from .config import CONFIG
-    from .data import create_dataloader, to_network_inputs
-    model, ckpt = load_for_evaluation(checkpoint_path, study_name, device)
-    if precision is not None:
-        model.set_precision(precision)
-    model.eval().freeze_inference()
-    dtype = model.model._rt.dtype
-    hyper = ckpt.get("hyperparameters", {})
-    bs = int(batch_size if batch_size is not None else hyper.get("batch_size", 16))
-    model_type = ckpt.get("model_type", "unet")
-    tag_emb = tag_of(*resolve_embedding_flags(ckpt, study_name))
-    trial_id = ckpt.get("trial_id", "unknown")
-    n_meta = ckpt.get("metadata_input_length", 4)
-    Co = model.model.final.weight.shape[0]
-    channels = list(CONFIG.dataset.target_channels)
-    if len(channels) != Co:
-        channels = [f"channel_{i}" for i in range(Co)]
-
-    if metrics_json is None:
-        default = os.path.join(processed_dir, "normalization_metrics.json")
-        metrics_json = default if os.path.exists(default) else ""
-    metrics = None
-    if metrics_json:
-        with open(metrics_json) as f:
-            metrics = json.load(f)
-    else:
-        log.warning("Normalization metrics not found. Using raw data.")
-    # un-normalise the temperature channels, leave NDVI as it is (get_unnormalized_data, :23-41)
-    scale = [float(metrics["temp_std"]) if metrics and "temp" in ch.lower() else 1.0 for ch in channels]
-    shift = [float(metrics["temp_mean"]) if metrics and "temp" in ch.lower() else 0.0 for ch in channels]
-
-    known = train_cities(processed_dir)
-    # the plain loader: DeviceLoader's 7-tuple drops cls_a, which the metrics need
-    loader = create_dataloader("test", bs, False, processed_dir=processed_dir, device=None)
-    dataset = loader.dataset
+    (model,), (ckpt,), channels, scale, shift, known, loader = open_test_split(
+        [checkpoint_path], processed_dir, batch_size=batch_size, precision=precision, study_name=study_name, metrics_json=metrics_json,
+        device=device)
     rows: List[dict] = []
-    sample_idx = 0
-    for host in loader:
-        batch = host.pin().to(device)
-        inputs, metadata, temp_series, _lengths, t1_dates, t2_dates, targets = to_network_inputs(batch, dtype)
-        if n_meta == 8:
-            metadata = torch.cat([metadata, t1_dates, t2_dates], dim=1)
+    for _host, batch, sample_idx, infos in walk_test_split(loader, known, device):
+        inputs, temp_series, metadata, targets = network_inputs(batch, model, ckpt, {})
         outputs = model(inputs, temp_series, metadata)
         m = eval_metrics(outputs, targets, batch.cls_a, scale, shift, batch.num_classes).cpu()      # the one copy of the batch
-        infos = []
-        for i in range(outputs.shape[0]):
-            t1y, t1m = int(host.t1_dates[i, 0]), int(host.t1_dates[i, 1])
-            t2y, t2m = int(host.t2_dates[i, 0]), int(host.t2_dates[i, 1])
-            info = dataset.get_metadata_from_idx(sample_idx + i)
-            infos.append({"is_known_city": info["city"] in known, "t1_year": t1y, "t1_month": t1m, "t2_year": t2y,
-                          "t2_month": t2m, "time_delta": t2y - t1y, **info})
         rows += metric_rows(m, sample_idx, channels, infos)
-        sample_idx += outputs.shape[0]
-    report_path, info_path = write_reports(rows, output_dir, study_name, model_type, tag_emb, trial_id, jobid)
+    report_path, info_path = write_reports(rows, output_dir, study_name, ckpt.get("model_type", "unet"),
+                                           tag_of(*resolve_embedding_flags(ckpt, study_name)), ckpt.get("trial_id", "unknown"), jobid)
     return {"rows": rows, "summary": summarize(rows), "report_path": report_path, "info_path": info_path}
 
 
@@ -334,9 +376,7 @@ def main(argv=None) -> int:
     p.add_argument("--output-dir", default="reports/tests")
     a = p.parse_args(argv)
     logging.basicConfig(level=logging.INFO, format="%(levelname)s %(message)s")
-    device = "cuda:0" if a.device.lower() == "gpu" else a.device
-    if device.lower() == "cpu":
-        p.error("this is the MI355X-native path: --device gpu (there is no CPU fallback)")
+    device = F_.argparse_device(p, a.device)
     res = evaluate_checkpoint(a.checkpoint_path, a.processed_dir, batch_size=a.batch_size, precision=a.precision,
                               study_name=a.study_name, jobid=a.jobid, output_dir=a.output_dir, metrics_json=a.metrics_json,
                               device=device)

@@ -51,18 +51,44 @@ def _require_cuda(t: torch.Tensor, what: str):
             "fallback. Move the module and its inputs to a 'cuda' (ROCm) device.")
 
 
+CPU_REFUSAL = "this is the MI355X-native path: --device gpu (there is no CPU fallback)"
+
+
+def argparse_device(parser, device: str) -> str:
+    """The ``--device`` of an argparse command line as a torch device name ('gpu' -> 'cuda:0'); 'cpu' is ``parser.error``."""
+    if device.lower() == "cpu":
+        parser.error(CPU_REFUSAL)
+    return "cuda:0" if device.lower() == "gpu" else device
+
+
+def typer_device(device: str) -> str:
+    """The same for a typer command line; 'cpu' is ``typer.BadParameter``."""
+    if device.lower() == "cpu":
+        import typer
+        raise typer.BadParameter(CPU_REFUSAL)
+    return "cuda:0" if device.lower() == "gpu" else device
+
+
+def _dev(t, what: str, dtype, shape=None) -> torch.Tensor:
+    """The argument check of the tools' entry points: a device tensor of ``dtype`` (and exactly ``shape``, if given), returned
+    detached and contiguous."""
+    if not isinstance(t, torch.Tensor):
+        raise TypeError(f"{what} must be a torch tensor on the device, got {type(t).__name__}")
+    _require_cuda(t, what)
+    if t.dtype != dtype:
+        raise TypeError(f"{what} must be {dtype}, got {t.dtype}")
+    if shape is not None and tuple(t.shape) != tuple(shape):
+        raise ValueError(f"{what} must be {tuple(shape)}, got {tuple(t.shape)}")
+    return t.detach().contiguous()
+
+
 def _device_planes(t, what: str, name: str, dtype, ndim: int, shape_doc: str) -> torch.Tensor:
     """The argument check of the analysis entry points that read whole planes (``mau_plane_moments``, ``mau_tile_stats``): a
     non-empty device tensor of ``dtype`` and rank ``ndim``, returned detached, contiguous and on a 16-byte aligned base -- the
     kernels' load width, and with it the order of their sums, is then a function of H * W alone."""
-    if not isinstance(t, torch.Tensor):
-        raise TypeError(f"{what}: {name} must be a torch.Tensor, got {type(t).__name__}")
-    _require_cuda(t, what)
-    if t.dtype != dtype:
-        raise TypeError(f"{what}: {name} must be {dtype}, got {t.dtype}")
+    t = _dev(t, f"{what}: {name}", dtype)
     if t.dim() != ndim or t.numel() == 0:
         raise ValueError(f"{what}: {name} must be a non-empty {shape_doc}, got {tuple(t.shape)}")
-    t = t.detach().contiguous()
     return t if t.data_ptr() % 16 == 0 else t.clone(memory_format=torch.contiguous_format)
 
 

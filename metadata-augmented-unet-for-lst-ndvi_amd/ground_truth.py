@@ -268,9 +268,7 @@ def main(argv=None) -> int:
     p.add_argument("--num-workers", type=int, default=0)
     p.add_argument("--device", default="gpu", help="'gpu' or a torch device name; this path has no CPU fallback")
     a = p.parse_args(argv)
-    device = "cuda:0" if a.device.lower() == "gpu" else a.device
-    if device.lower() == "cpu":
-        p.error("this is the MI355X-native path: --device gpu (there is no CPU fallback)")
+    device = F_.argparse_device(p, a.device)
     channels = list(CONFIG.dataset.target_channels)
     print(f"Target Channels: {channels}")
     try:

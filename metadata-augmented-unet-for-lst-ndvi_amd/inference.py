@@ -10,6 +10,8 @@ from __future__ import annotations
 
 import torch
 
+from ._capture import freeze, warm_up_and_capture
+
 
 class GraphedInference:
     """``GraphedInference(model, maps, temp_series, metadata)(maps, temp_series, metadata) -> output``.
@@ -24,20 +26,11 @@ class GraphedInference:
                  warmup: int = 2, clone_output: bool = True):
         if not maps.is_cuda:
             raise RuntimeError("GraphedInference needs inputs on the MI355X ('cuda') device; there is no CPU fallback")
-        self.model = model.eval()
+        self.model = model
         self.clone_output = clone_output                 # False: __call__ returns the session's own output buffer, valid until the next call
-        if hasattr(self.model, "freeze_inference"):
-            self.model.freeze_inference(True)           # packed weights / folded BN coefficients computed once, outside the graph
+        freeze(model)
         self._in = [maps.detach().clone(), temp_series.detach().clone(), metadata.detach().clone()]
-        side = torch.cuda.Stream(device=maps.device)
-        side.wait_stream(torch.cuda.current_stream())
-        with torch.cuda.stream(side), torch.no_grad():
-            for _ in range(max(1, warmup)):            # packs weights, sets kernel attributes, warms the allocator
-                self.model(*self._in)
-        torch.cuda.current_stream().wait_stream(side)
-        self.graph = torch.cuda.CUDAGraph()
-        with torch.no_grad(), torch.cuda.graph(self.graph):
-            self._out = self.model(*self._in)
+        self.graph, self._out = warm_up_and_capture(lambda: self.model(*self._in), maps.device, warmup)
 
     @property
     def inputs(self):

@@ -26,6 +26,7 @@ import torch
 
 from . import functional as F_
 from . import scenario as S
+from ._capture import PinnedStage, freeze, warm_up_and_capture
 from .config import CONFIG
 from .functional import Act, call, dtype_code, lib, pad8
 
@@ -165,7 +166,7 @@ def gather(dw_t1, dw_t2, rgb, ndvi, temp, origins, window: int, ncls: int, metri
     ``data.pack_tiles`` on the cropped class maps and ``normalized_planes_host`` of the cropped raw planes."""
     dw_t1, rgb, ndvi, temp = S._tile(dw_t1, rgb, ndvi, temp)
     Hr, Wr = dw_t1.shape
-    dw_t2 = dw_t1 if dw_t2 is None else S._dev(dw_t2, "dw_t2", torch.uint8, (Hr, Wr))
+    dw_t2 = dw_t1 if dw_t2 is None else F_._dev(dw_t2, "dw_t2", torch.uint8, (Hr, Wr))
     T, ncls = int(window), _ncls(ncls)
     if not 1 <= T <= min(Hr, Wr, MAX_WINDOW):
         raise ValueError(f"gather: a window of {T} does not fit a region of {Hr} x {Wr} (windows of at most {MAX_WINDOW}); a region "
@@ -194,7 +195,7 @@ def stitch(win: torch.Tensor, ys, xs, shape: Tuple[int, int], ramp: int) -> torc
     at (ys[iy], xs[ix]) -> the blended (C, Hr, Wr) fp32 map, bit-identical to ``stitch_host``.  ``ys`` and ``xs`` are HOST arrays:
     the device cannot check them, so this wrapper does -- strictly ascending, from 0 to Hr - T / Wr - T, no gap wider than T and
     at most three windows over a coordinate (what ``window_origins`` gives)."""
-    win = S._dev(win, "win", torch.float32)
+    win = F_._dev(win, "win", torch.float32)
     Hr, Wr = int(shape[0]), int(shape[1])
     if win.dim() != 4 or win.shape[2] != win.shape[3] or win.shape[1] < 1:
         raise ValueError(f"win must be (ny * nx, C, T, T), got {tuple(win.shape)}")
@@ -261,14 +262,11 @@ class RegionSession:
         ny, nx = self.ys.size, self.xs.size
         self.windows = nWin = ny * nx
         self._ncls = _ncls(S._palette(palette).shape[0])
-        self.model = model.eval()
-        if hasattr(self.model, "freeze_inference"):
-            self.model.freeze_inference(True)
-        net = getattr(self.model, "model", self.model)
-        self.dtype = net._rt.dtype
+        self.model = model
+        self.dtype = freeze(model)
         self._region = tuple(t.detach().clone() for t in (dw_t1, rgb, ndvi, temp))
-        self._dw_t2 = (dw_t1 if dw_t2 is None else S._dev(dw_t2, "dw_t2", torch.uint8, (Hr, Wr))).detach().clone()
-        self._temp_orig = self._region[3] if temp_orig is None else S._dev(temp_orig, "temp_orig", torch.float32, (Hr, Wr)).detach().clone()
+        self._dw_t2 = (dw_t1 if dw_t2 is None else F_._dev(dw_t2, "dw_t2", torch.uint8, (Hr, Wr))).detach().clone()
+        self._temp_orig = self._region[3] if temp_orig is None else F_._dev(temp_orig, "temp_orig", torch.float32, (Hr, Wr)).detach().clone()
         self._norm = S._const(S._norm_row(metrics), torch.float64, dev)
         self._mean, self._std = float(metrics["temp_mean"]), float(metrics["temp_std"])
         self._ys, self._xs = S._const(self.ys, torch.int32, dev), S._const(self.xs, torch.int32, dev)
@@ -285,17 +283,8 @@ class RegionSession:
         self._md_all = torch.cat([md, md[-1:].expand(pad, -1)]).contiguous() if md.shape[0] > 1 else None      # one row per window
         self._md = (md.expand(B, -1) if self._md_all is None else self._md_all[:B]).contiguous().clone()
         self._ts = temp_series.detach().float().reshape(1, -1).expand(B, -1).contiguous()
-        self._stage = torch.empty((Hr, Wr), dtype=torch.uint8).pin_memory()             # a host class map travels through pinned memory
-        self._staged = torch.cuda.Event()
-        side = torch.cuda.Stream(device=dev)
-        side.wait_stream(torch.cuda.current_stream())
-        with torch.cuda.stream(side), torch.no_grad():
-            for _ in range(max(1, warmup)):            # packs weights, sets kernel attributes, warms the allocator
-                self._run()
-        torch.cuda.current_stream().wait_stream(side)
-        self.graph = torch.cuda.CUDAGraph()
-        with torch.no_grad(), torch.cuda.graph(self.graph):
-            self._out = self._run()
+        self._stage = PinnedStage((Hr, Wr), torch.uint8)                                # a host class map travels through pinned memory
+        self.graph, self._out = warm_up_and_capture(self._run, dev, warmup)
 
     def _run(self) -> torch.Tensor:
         x = _gather(self._region[0], self._dw_t2, *self._region[1:], self._origins, self._norm, self.window, self._ncls, self.dtype,
@@ -310,10 +299,7 @@ class RegionSession:
         if isinstance(dw_t2, torch.Tensor) and dw_t2.is_cuda:
             self._dw_t2.copy_(dw_t2, non_blocking=True)
         else:
-            self._staged.synchronize()                  # the previous call's copy out of the pinned buffer has finished
-            self._stage.copy_(dw_t2 if isinstance(dw_t2, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(dw_t2)))
-            self._dw_t2.copy_(self._stage, non_blocking=True)
-            self._staged.record()
+            self._stage.upload(dw_t2, self._dw_t2)
 
     @torch.no_grad()
     def __call__(self, dw_t2=None) -> RegionResult:
@@ -384,10 +370,8 @@ def _cli():
              window: int = CONFIG.model.img_size, overlap: int = typer.Option(-1, help="pixels neighbouring windows share; -1 = window // 4"),
              batch: int = 8, precision: str = "fp16", output: str = "", device: str = "gpu"):
         """The forecast of a checkpoint for a whole region: overlapping windows at the trained resolution, blended."""
-        if device.lower() == "cpu":
-            raise typer.BadParameter("this is the MI355X-native path: --device gpu (there is no CPU fallback)")
         res = run_region(checkpoint, region, palette_json, metrics_json, window, None if overlap < 0 else overlap, batch, precision, output,
-                         "cuda:0" if device.lower() == "gpu" else device)
+                         F_.typer_device(device))
         ny, nx = len(res["ys"]), len(res["xs"])
         typer.echo(f"region {res['output'].shape[2]} x {res['output'].shape[3]}: {ny} x {nx} windows of {int(res['window'])} "
                    f"(overlap {int(res['overlap'])}, ramp {int(res['ramp'])}), {-(-ny * nx // batch)} batches of {batch}")

@@ -28,7 +28,8 @@ import numpy as np
 import torch
 
 from . import functional as F_
-from .functional import Act, call, dtype_code, lib, pad8
+from ._capture import PinnedStage, freeze, warm_up_and_capture
+from .functional import Act, _dev, call, dtype_code, lib, pad8
 
 N_CONT = 5               # rgb (3) + ndvi + temperature
 METRIC_KEYS = ("rgb_mean", "rgb_std", "temp_mean", "temp_std", "meta_mean", "meta_std", "temp_series_mean", "temp_series_std")
@@ -146,17 +147,6 @@ def normalize_temp_series(ts, metrics: dict) -> np.ndarray:
 # --------------------------------------------------------------------------- #
 # the two launches
 # --------------------------------------------------------------------------- #
-def _dev(t, what: str, dtype, shape=None) -> torch.Tensor:
-    if not isinstance(t, torch.Tensor):
-        raise TypeError(f"{what} must be a torch tensor on the device, got {type(t).__name__}")
-    F_._require_cuda(t, what)
-    if t.dtype != dtype:
-        raise TypeError(f"{what} must be {dtype}, got {t.dtype}")
-    if shape is not None and tuple(t.shape) != tuple(shape):
-        raise ValueError(f"{what} must be {tuple(shape)}, got {tuple(t.shape)}")
-    return t.contiguous()
-
-
 def _const(v, dtype, dev) -> torch.Tensor:
     """A small host array (or device tensor) as a contiguous device tensor."""
     if isinstance(v, torch.Tensor):
@@ -293,12 +283,9 @@ class ScenarioSession:
         _check_metrics(metrics)
         dev = dw_t1.device
         N, (Hc, Wc) = int(scenarios), (int(canvas_shape[0]), int(canvas_shape[1]))
-        self.model = model.eval()
+        self.model = model
         self.clone_output = clone_output
-        if hasattr(self.model, "freeze_inference"):
-            self.model.freeze_inference(True)
-        net = getattr(self.model, "model", self.model)
-        self.dtype = net._rt.dtype
+        self.dtype = freeze(model)
         self._tile = tuple(t.detach().clone() for t in (dw_t1, rgb, ndvi, temp))
         self._temp_orig = self._tile[3] if temp_orig is None else _dev(temp_orig, "temp_orig", torch.float32, tuple(dw_t1.shape)).detach().clone()
         self._tables = _Tables(dw_t1.shape, (Hc, Wc), palette, metrics, dev)
@@ -306,19 +293,10 @@ class ScenarioSession:
         self._md = metadata.detach().float().reshape(1, -1).expand(N, -1).contiguous()
         self._ts = temp_series.detach().float().reshape(1, -1).expand(N, -1).contiguous()
         self._canvas = torch.zeros((N, Hc, Wc, 4), dtype=torch.uint8, device=dev)
-        self._stage = torch.empty((N, Hc, Wc, 4), dtype=torch.uint8).pin_memory()       # host canvases travel through pinned memory
-        self._staged = torch.cuda.Event()
+        self._stage = PinnedStage((N, Hc, Wc, 4), torch.uint8)                          # host canvases travel through pinned memory
         # the tickets of the captured reduction are the session's own: a replay never shares them with a launch on another stream
         self._tickets = torch.zeros(lib.mau_reduce_tickets_elems(), dtype=torch.int32, device=dev)
-        side = torch.cuda.Stream(device=dev)
-        side.wait_stream(torch.cuda.current_stream())
-        with torch.cuda.stream(side), torch.no_grad():
-            for _ in range(max(1, warmup)):            # packs weights, sets kernel attributes, warms the allocator
-                self._run()
-        torch.cuda.current_stream().wait_stream(side)
-        self.graph = torch.cuda.CUDAGraph()
-        with torch.no_grad(), torch.cuda.graph(self.graph):
-            self._out = self._run()
+        self.graph, self._out = warm_up_and_capture(self._run, dev, warmup)
 
     def _run(self) -> ScenarioResult:
         x, dw_t2 = _pack(*self._tile, self._canvas, self._tables, self.dtype)
@@ -345,10 +323,7 @@ class ScenarioSession:
             if src.data_ptr() != self._canvas.data_ptr():
                 self._canvas.copy_(src, non_blocking=True)
         else:
-            self._staged.synchronize()                  # the previous call's copy out of the pinned buffer has finished
-            self._stage.copy_(src if isinstance(src, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(src)))
-            self._canvas.copy_(self._stage, non_blocking=True)
-            self._staged.record()
+            self._stage.upload(src, self._canvas)
         self.graph.replay()
         return self._out.clone() if self.clone_output else self._out
 
@@ -401,9 +376,7 @@ def _cli():
              metrics_json: str = typer.Option(..., help="normalization_metrics.json"),
              precision: str = "fp16", output: str = "", device: str = "gpu"):
         """One scenario (canvas edit -> forecast and temperature change) of a checkpoint on one tile."""
-        if device.lower() == "cpu":
-            raise typer.BadParameter("this is the MI355X-native path: --device gpu (there is no CPU fallback)")
-        res = run_tile(checkpoint, tile, palette_json, metrics_json, precision, output, "cuda:0" if device.lower() == "gpu" else device)
+        res = run_tile(checkpoint, tile, palette_json, metrics_json, precision, output, F_.typer_device(device))
         for n in range(res["stats"].shape[0]):
             typer.echo("scenario %d: " % n + ", ".join(f"{name} {res[name][n]:.6g}" for name in STAT_NAMES))
         if output:

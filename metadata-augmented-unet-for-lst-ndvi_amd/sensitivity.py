@@ -255,20 +255,10 @@ def load_for_sensitivity(checkpoint_path: str, seq_len: int, study_name: str = "
     test/metadata_sensitivity.py:79-133 does (embedding flags, ``model_type`` default 'unet', ``metadata_input_length``
     default 4, ``temporal_dim`` / ``meta_dim`` / ``lstm_hidden`` defaults 16 / 8 / 32).  Input channels and filter width are
     read off the first convolution's weight (the reference takes them from its CONFIG and the constructor default)."""
-    from .checkpoint import resolve_embedding_flags
-    ckpt = torch.load(checkpoint_path, map_location="cpu", weights_only=False)
-    hyper = ckpt.get("hyperparameters", {})
-    t_emb, m_emb = resolve_embedding_flags(ckpt, study_name)
+    from .checkpoint import SENSITIVITY_WIDTHS, load_reference_checkpoint, resolve_embedding_flags
+    model, ckpt = load_reference_checkpoint(checkpoint_path, seq_len, SENSITIVITY_WIDTHS, study_name, device)
     model_type = ckpt.get("model_type", "unet")
-    n_meta = ckpt.get("metadata_input_length", 4)
-    sd = ckpt["model_state_dict"]
-    w0 = sd["model.conv0_0.conv1.weight"]
-    out_channels = sd["model.final.weight"].shape[0]
-    model = UrbanPredictor(model_type=model_type, spatial_channels=w0.shape[1], seq_len=seq_len, temporal_dim=hyper.get("temporal_dim", 16),
-                           meta_features=n_meta, meta_dim=hyper.get("meta_dim", 8), lstm_dim=hyper.get("lstm_hidden", 32),
-                           out_channels=out_channels, base_filters=w0.shape[0], temporal_embeddings=t_emb, metadata_embeddings=m_emb)
-    model.load_state_dict(sd)
-    return model.to(device).eval(), model_name_of(t_emb, m_emb, model_type), model_type, n_meta
+    return model, model_name_of(*resolve_embedding_flags(ckpt, study_name), model_type), model_type, ckpt.get("metadata_input_length", 4)
 
 
 def run_cli(checkpoint: str, samples: int, output_dir: str, precision: str = "bf16", heatmaps: int = 0, metrics_json: str = "",
@@ -276,6 +266,7 @@ def run_cli(checkpoint: str, samples: int, output_dir: str, precision: str = "bf
             chunk: int = CHUNK) -> str:
     """Body of the CLI; returns the path of the JSON it wrote."""
     from .config import CONFIG
+    from .evaluate import temperature_coeffs
     ds = CONFIG.dataset
     tile = ds.image_shape_edge if tile is None else tile
     seq_len = ds.temporal_length if seq_len is None else seq_len
@@ -291,9 +282,8 @@ def run_cli(checkpoint: str, samples: int, output_dir: str, precision: str = "bf
             metrics = json.load(f)
     else:                                                            # identity normalisation
         metrics = {"meta_mean": [0.0] * 4, "meta_std": [1.0] * 4, "temp_mean": 0.0, "temp_std": 1.0}
-    # un-normalise the temperature channels, leave NDVI as it is (test/metadata_sensitivity.py:22-39)
-    scale = [float(metrics.get("temp_std", 1.0)) if "temp" in ch.lower() else 1.0 for ch in channels]
-    shift = [float(metrics.get("temp_mean", 0.0)) if "temp" in ch.lower() else 0.0 for ch in channels]
+    # (test/metadata_sensitivity.py:22-39; a metrics file without the temperature keys leaves the channel as it is)
+    scale, shift = temperature_coeffs(channels, {"temp_mean": 0.0, "temp_std": 1.0, **metrics})
     report = SensitivityReport(model_name, model_type, channels)
     gen = torch.Generator().manual_seed(CONFIG.seed if seed is None else seed)
     in_ch = net.conv0_0.conv1.in_channels

@@ -38,7 +38,6 @@ from __future__ import annotations
 import argparse
 import csv
 import itertools
-import json
 import logging
 import math
 import os
@@ -48,8 +47,8 @@ import numpy as np
 import torch
 
 from . import functional as F_
-from .evaluate import (DW_CLASS_NAMES, MAX_CLASSES, _HEAD, _coeffs, load_for_evaluation, metric_rows, report_paths, tag_of,
-                       train_cities, write_reports, EvalMetrics)
+from .evaluate import (DW_CLASS_NAMES, MAX_CLASSES, _HEAD, _checked_args, metric_rows, network_inputs, open_test_split, report_paths,
+                       tag_of, walk_test_split, write_reports, EvalMetrics)
 from .functional import call, lib
 
 log = logging.getLogger(__name__)
@@ -396,26 +395,9 @@ def eval_metrics_multi(outputs: torch.Tensor, targets: torch.Tensor, cls: torch.
     """The rows of M models against one target in ONE launch: outputs (M, B, C, H, W) fp32, targets (B, C, H, W) fp32, cls (B, H, W)
     uint8, all on the device -> (M, B, C, row_elems) fp64 device tensor; ``rows[m]`` has exactly the bits of
     ``evaluate.eval_metrics(outputs[m], targets, cls, ...).rows``, whatever M and the model's place.  1 <= M <= 8."""
-    for t, what in ((outputs, "outputs"), (targets, "targets"), (cls, "cls")):
-        F_._require_cuda(t, f"eval_metrics_multi({what})")
-    if outputs.dtype != torch.float32 or targets.dtype != torch.float32:
-        raise TypeError(f"eval_metrics_multi: outputs and targets must be float32, got {outputs.dtype} and {targets.dtype}")
-    if cls.dtype != torch.uint8:
-        raise TypeError(f"eval_metrics_multi: cls must be uint8, got {cls.dtype}")
-    if outputs.dim() != 5 or targets.dim() != 4 or outputs.shape[1:] != targets.shape:
-        raise ValueError(f"eval_metrics_multi: outputs must be (M, B, C, H, W) and targets (B, C, H, W), got {tuple(outputs.shape)} and {tuple(targets.shape)}")
+    outputs, targets, cls, scale, shift = _checked_args("eval_metrics_multi", outputs, targets, cls, scale, shift, num_classes, MAX_MODELS)
     M, B, C, H, W = outputs.shape
-    if not 1 <= M <= MAX_MODELS:
-        raise ValueError(f"eval_metrics_multi: M must be in [1, {MAX_MODELS}], got {M}")
-    if tuple(cls.shape) != (B, H, W):
-        raise ValueError(f"eval_metrics_multi: cls must be {(B, H, W)}, got {tuple(cls.shape)}")
-    if not 1 <= num_classes <= MAX_CLASSES:
-        raise ValueError(f"eval_metrics_multi: num_classes must be in [1, {MAX_CLASSES}], got {num_classes}")
-    if B * C * H * W == 0:
-        raise ValueError("eval_metrics_multi: empty batch")
     dev = outputs.device
-    outputs, targets, cls = outputs.detach().contiguous(), targets.detach().contiguous(), cls.contiguous()
-    scale, shift = _coeffs(scale, C, dev, "scale", 1.0), _coeffs(shift, C, dev, "shift", 0.0)
     rows = torch.empty((M, B, C, lib.mau_eval_metrics_row_elems(num_classes)), dtype=torch.float64, device=dev)
     need = lib.mau_eval_metrics_multi_ws_elems(M, B, C, H, W, num_classes)
     if ws is None or ws.numel() < need:
@@ -477,70 +459,26 @@ def compare_checkpoints(checkpoint_paths: Sequence[str], processed_dir: str, *, 
     'tests', 'rows' (per model), 'report_paths', 'info_paths', 'tests_path'}.  batch_size: default the first checkpoint's
     ``hyperparameters.batch_size``, else 16."""
     from .checkpoint import resolve_embedding_flags
-    from .config import CONFIG
-    from .data import create_dataloader, to_network_inputs
     M = len(checkpoint_paths)
     if not 1 <= M <= MAX_MODELS:
         raise ValueError(f"compare_checkpoints: between 1 and {MAX_MODELS} checkpoints, got {M}")
-    models, ckpts = [], []
-    for path in checkpoint_paths:
-        model, ckpt = load_for_evaluation(path, study_name, device)
-        if precision is not None:
-            model.set_precision(precision)
-        model.eval().freeze_inference()
-        models.append(model)
-        ckpts.append(ckpt)
-    Co = models[0].model.final.weight.shape[0]
-    if any(m.model.final.weight.shape[0] != Co for m in models):
-        raise ValueError("compare_checkpoints: the checkpoints do not have the same number of output channels")
-    bs = int(batch_size if batch_size is not None else ckpts[0].get("hyperparameters", {}).get("batch_size", 16))
-    channels = list(CONFIG.dataset.target_channels)
-    if len(channels) != Co:
-        channels = [f"channel_{i}" for i in range(Co)]
+    models, ckpts, channels, scale, shift, known, loader = open_test_split(
+        checkpoint_paths, processed_dir, batch_size=batch_size, precision=precision, study_name=study_name, metrics_json=metrics_json,
+        device=device)
+    Co = len(channels)
     idents = [(ck.get("model_type", "unet"), tag_of(*resolve_embedding_flags(ck, study_name)), ck.get("trial_id", "unknown")) for ck in ckpts]
     paths = [report_paths(output_dir, study_name, mt, tag, trial, jobid) for mt, tag, trial in idents]
     names = [os.path.basename(p[0]).replace("_evaluation.csv", "") for p in paths]                 # statistical_tests.py:193
     if len(set(names)) != M:
         raise ValueError(f"compare_checkpoints: the checkpoints' reports would overwrite each other ({names}): give them distinct trial ids")
-
-    if metrics_json is None:
-        default = os.path.join(processed_dir, "normalization_metrics.json")
-        metrics_json = default if os.path.exists(default) else ""
-    metrics = None
-    if metrics_json:
-        with open(metrics_json) as f:
-            metrics = json.load(f)
-    else:
-        log.warning("Normalization metrics not found. Using raw data.")
-    scale = [float(metrics["temp_std"]) if metrics and "temp" in ch.lower() else 1.0 for ch in channels]
-    shift = [float(metrics["temp_mean"]) if metrics and "temp" in ch.lower() else 0.0 for ch in channels]
-
-    known = train_cities(processed_dir)
-    loader = create_dataloader("test", bs, False, processed_dir=processed_dir, device=None)
-    dataset = loader.dataset
     rows: List[List[dict]] = [[] for _ in range(M)]
     stats, buf, ws = None, None, None
-    sample_idx = 0
-    for host in loader:
-        batch = host.pin().to(device)
+    for _host, batch, sample_idx, infos in walk_test_split(loader, known, device):
         packed: Dict[torch.dtype, tuple] = {}                       # the batch is packed once per network dtype
-        B = int(host.t1_dates.shape[0])
-        infos, gids = [], []
-        for i in range(B):
-            t1y, t1m = int(host.t1_dates[i, 0]), int(host.t1_dates[i, 1])
-            t2y, t2m = int(host.t2_dates[i, 0]), int(host.t2_dates[i, 1])
-            info = dataset.get_metadata_from_idx(sample_idx + i)
-            infos.append({"is_known_city": info["city"] in known, "t1_year": t1y, "t1_month": t1m, "t2_year": t2y,
-                          "t2_month": t2m, "time_delta": t2y - t1y, **info})
-            gids.append(group_id(info["city"] in known, t1y))
+        gids = [group_id(info["is_known_city"], info["t1_year"]) for info in infos]
         targets = None
         for m, model in enumerate(models):
-            dtype = model.model._rt.dtype
-            if dtype not in packed:
-                packed[dtype] = to_network_inputs(batch, dtype)
-            inputs, metadata, temp_series, _lengths, t1_dates, t2_dates, targets = packed[dtype]
-            if ckpts[m].get("metadata_input_length", 4) == 8:
-                metadata = torch.cat([metadata, t1_dates, t2_dates], dim=1)
+            inputs, temp_series, metadata, targets = network_inputs(batch, model, ckpts[m], packed)
             out = model(inputs, temp_series, metadata)
             if buf is None or buf.shape[1:] != out.shape:
                 buf = torch.empty((M,) + tuple(out.shape), dtype=torch.float32, device=out.device)
@@ -555,7 +493,6 @@ def compare_checkpoints(checkpoint_paths: Sequence[str], processed_dir: str, *, 
         host_rows = mrows.cpu()                                     # the one copy of the batch
         for m in range(M):
             rows[m] += metric_rows(EvalMetrics(host_rows[m], batch.num_classes), sample_idx, channels, infos)
-        sample_idx += B
     if stats is None:
         raise ValueError(f"compare_checkpoints: the test split of {processed_dir} is empty")
     table = stats.result()                                          # the one read-back of the table
@@ -583,9 +520,7 @@ def main(argv=None) -> int:
     p.add_argument("--output-dir", default="reports/tests")
     a = p.parse_args(argv)
     logging.basicConfig(level=logging.INFO, format="%(levelname)s %(message)s")
-    device = "cuda:0" if a.device.lower() == "gpu" else a.device
-    if device.lower() == "cpu":
-        p.error("this is the MI355X-native path: --device gpu (there is no CPU fallback)")
+    device = F_.argparse_device(p, a.device)
     if len(a.checkpoint_paths) > MAX_MODELS:
         p.error(f"at most {MAX_MODELS} checkpoints")
     res = compare_checkpoints(a.checkpoint_paths, a.processed_dir, batch_size=a.batch_size, precision=a.precision,

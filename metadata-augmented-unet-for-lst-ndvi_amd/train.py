@@ -27,6 +27,7 @@ from . import compute_loss_l1_grad_ssim, compute_loss_mse, compute_loss_mse_grad
 from . import data as data_
 from .checkpoint import build_hyperparameters, save_checkpoint
 from .config import CONFIG
+from .functional import typer_device
 from .dist import GradSync, init_process_group_from_env
 from .losses import ALL_LOSS_TERMS, TERM_MSE_GRADIENT_TOTAL, loss_terms
 from .metrics import RunningLoss
@@ -137,8 +138,7 @@ def run(device: str = "", wandblog: bool = False, n_trials: int = 1, force_study
     if not force_study_name:                                                                  # src/train.py:79-87
         study_name += "-emb" if temporal_embeddings and metadata_embeddings else "-tempemb" if temporal_embeddings \
             else "-metaemb" if metadata_embeddings else "-noemb"
-    if device.lower() == "cpu":
-        raise typer.BadParameter("this is the MI355X-native path: --device gpu (there is no CPU fallback)")
+    typer_device(device)
     if processed_dir is not None:                    # before anything touches the GPU: a wrong path is the likeliest mistake
         for split in ("train", "val"):
             if not os.path.isdir(os.path.join(processed_dir, split)):

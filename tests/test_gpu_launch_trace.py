@@ -7,20 +7,17 @@ A call is recorded as ``[name, args...]``; ``_lib.PROTOTYPES[name]`` tells point
   * a pointer as 0 / 1 (null or not) -- addresses differ from run to run, whether an optional operand is passed does not;
   * the trailing stream as "main" (the stream current when the case started) or "side".
 The real call still runs.  The SyncBN branch needs more than one GPU: tests/test_dist_gloo.py, tests/test_gpu_dist_rehearsal.py."""
-import contextlib
-import ctypes
 import json
 import os
 
 import pytest
 import torch
 
+from tests.helpers import first_difference, patched, recorded_calls
+
 pytestmark = pytest.mark.gpu
 
 GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "launch_trace.json")
-
-HOST_ONLY = ("mau_conv3x3_pack_desc_fill",)           # fills a host table: its last argument is no stream
-_FLOATS = (ctypes.c_float, ctypes.c_double)
 
 # every hook of functional pinned to its default, so that a case's ``hooks`` are the only difference from the first case
 DEFAULT_HOOKS = dict(_OVERLAP_WGRAD=2, _FUSED_REDUCE=True, _FUSED_BN=True, _FUSED_UP=True, _PACK_MULTI=True, _INFER_POOL_FUSED=True,
@@ -50,40 +47,9 @@ CASES = {
 }
 
 
-@contextlib.contextmanager
-def patched(mod, **attrs):
-    old = {k: getattr(mod, k) for k in attrs}
-    try:
-        for k, v in attrs.items():
-            setattr(mod, k, v)
-        yield
-    finally:
-        for k, v in old.items():
-            setattr(mod, k, v)
-
-
-def encode(prototypes, name, args, main):
-    argtypes = prototypes[name][1]
-    assert len(args) == len(argtypes), (name, len(args), len(argtypes))
-    row = [name]
-    last = len(args) - 1
-    for i, (a, ty) in enumerate(zip(args, argtypes)):
-        if ty is ctypes.c_void_p:
-            if i == last and name not in HOST_ONLY:
-                row.append("main" if (a or 0) == main else "side")
-            else:
-                row.append(1 if a else 0)
-        elif ty in _FLOATS:
-            row.append(float(a).hex())
-        else:
-            row.append(int(a))
-    return row
-
-
 def record_case(mau, case):
     """One fresh network: a training step (``eval_grad``: the same in eval mode), an eval no-grad forward, a frozen one."""
     from mau_amd import functional as F_
-    rows = []
     torch.manual_seed(11)
     H, W = case["size"]
     g = torch.Generator().manual_seed(12)
@@ -93,14 +59,7 @@ def record_case(mau, case):
     net = mau.UrbanPredictor(case["model_type"], 6, 10, tdim, 4, mdim, 24, 2, base_filters=case["base_filters"], **case["flags"])
     net = net.cuda().set_precision(case["prec"])
     torch.cuda.synchronize()
-    main = torch.cuda.current_stream().cuda_stream
-    real = F_.call
-
-    def spy(name, *args):
-        rows.append(encode(mau._lib.PROTOTYPES, name, args, main))
-        return real(name, *args)
-
-    with patched(F_, **dict(DEFAULT_HOOKS, **case.get("hooks", {}))), patched(F_, call=spy):
+    with patched(F_, **dict(DEFAULT_HOOKS, **case.get("hooks", {}))), recorded_calls(mau) as rows:
         net.eval() if case.get("eval_grad") else net.train()
         mau.compute_loss_mse(net(x, ts, md), tgt)["total"].backward()
         net.eval()
@@ -132,8 +91,5 @@ def test_golden_holds_every_case(golden):
 
 @pytest.mark.parametrize("name", list(CASES))
 def test_launch_trace_matches_the_recorded_one(mau, golden, name):
-    got, want = record_case(mau, CASES[name]), golden["cases"][name]
-    for i, (a, b) in enumerate(zip(got, want)):
-        assert a == b, f"{name}: call {i} differs\n   now: {a}\n  then: {b}\n  (before it: {got[max(0, i - 3):i]})"
-    n = min(len(got), len(want))
-    assert len(got) == len(want), f"{name}: {len(got)} calls now, {len(want)} recorded; the first one more: {(got[n:] + want[n:])[0]}"
+    diff = first_difference(record_case(mau, CASES[name]), golden["cases"][name], name)
+    assert diff is None, diff
