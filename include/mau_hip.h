@@ -716,6 +716,39 @@ int mau_raw_tile_process(const unsigned char* dw_t1, const unsigned char* dw_t2,
                          const float* ndvi_t2, const float* temp_t1, const float* temp_t2, const double* norm, double* rows, float* cont,
                          float* targets, double* ws, unsigned* tickets, int B, int64_t HW, int num_classes, mau_stream_t stream);
 
+/* ---- climate stage (src/data/process_temperature.py: the 1901-1950 baseline of :23-33, the normalised anomalies of :48-55,
+ *      TemperatureQuery.query of :93-114).  Additive to ABI 5 ----
+ * x (T,G) fp32: the year files concatenated along time, time-major, the G = lat * lon cells of a month contiguous.  A baseline row
+ * is mau_climate_row_elems() = 4 fp64 per cell: [0] n, the number of non-NaN months  [1] their mean  [2] M2 = sum (x - mean)^2 over
+ * them  [3] the number of NaN months (n + [3] = T).
+ *
+ * mau_climate_baseline: x (T,G) -> rows (G,4).  One thread per cell, consecutive threads on consecutive cells; two passes over time
+ * in TIME ORDER in fp64, nothing contracted: sum of the non-NaN months, mean = sum / n, then M2.  A NaN is skipped and counted
+ * (skipna); an infinity is not skipped and propagates (mean +-inf or NaN, M2 NaN), as np.nanmean lets it; a cell without a month
+ * gets mean = M2 = NaN.  No workspace, no atomics: a cell's bits depend on its own column only -- not on G, not on its place.
+ *
+ * mau_climate_normalise: out (T,G) fp32 = (float)(((double)x - mean) / sqrt(M2 / n)), fp64 and rounded once, with the cell's row of
+ * `rows`.  std == 0 and an empty cell give what IEEE division gives (+-inf, NaN).  16-byte accesses (four cells per thread) when
+ * G % 4 == 0 and x and out are 16-byte aligned, 4-byte ones otherwise: the same bits either way.  T <= 65535 * 64.
+ *
+ * mau_climate_series: the batched nearest-grid-point query.  x is the RAW grid, rows its baseline; per query n the DEVICE arrays
+ * cell[n] (the cell, in [0,G)) and keep[n] (the months to keep, in [0,T]; clamped to that range).  series (N,Tpad) fp32:
+ * series[n][t] for t < keep[n] is the expression of mau_climate_normalise on x[t][cell[n]] (the same bits), 0 for t >= keep[n]
+ * (pad_sequence's padding).  srows (N,4) fp64: the moment row (mau_moments_row_elems: n, mean, M2, non-finite values) of the kept
+ * values of series[n], two passes, sums in a fixed order (one 256-thread workgroup per query, a series is one chunk of
+ * mau_plane_moments: T <= mau_climate_series_max_months() = 4096).  keep[n] == 0 gives the row (0, NaN, 0, 0).  A cell outside
+ * [0,G) cannot be refused without a read-back: its kept values are NaN and its row is (0, NaN, 0, 0); nothing is read out of
+ * bounds.  No host work per query, no synchronisation: the launch can be captured.  A query's bits depend on its own cell and keep
+ * only -- not on N, not on its place.
+ * Refused (MAU_ERR_ARG): a NULL pointer, T, G or N <= 0, G or N > 2^30, an fp32 / int32 buffer not 4-byte or an fp64 buffer not
+ * 8-byte aligned; for the series T > 4096 and Tpad < T. */
+int mau_climate_row_elems(void);
+int mau_climate_series_max_months(void);
+int mau_climate_baseline(const float* x, double* rows, int T, int G, mau_stream_t stream);
+int mau_climate_normalise(const float* x, const double* rows, float* out, int T, int G, mau_stream_t stream);
+int mau_climate_series(const float* x, const double* rows, const int* cell, const int* keep, float* series, double* srows, int N,
+                       int T, int G, int Tpad, mau_stream_t stream);
+
 /* ---- loss: F.mse_loss (src/utils/losses.py:27-39) -------------------------- */
 /* loss[0] = mean((out-tgt)^2) (fp64 accumulation, fixed order); dout (optional) = 2*(out-tgt)/n;
  * partial: fp64 workspace of mau_mse_blocks(n) elements. */

@@ -150,6 +150,11 @@ PROTOTYPES = {
     "mau_raw_tile_row_elems": (_i, []),
     "mau_raw_tile_ws_elems": (_sz, [_i, _i64]),
     "mau_raw_tile_process": (_i, [_p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _i, _i64, _i, _p]),
+    "mau_climate_row_elems": (_i, []),
+    "mau_climate_series_max_months": (_i, []),
+    "mau_climate_baseline": (_i, [_p, _p, _i, _i, _p]),
+    "mau_climate_normalise": (_i, [_p, _p, _p, _i, _i, _p]),
+    "mau_climate_series": (_i, [_p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _p]),
     "mau_mse_blocks": (_i, [_i64]),
     "mau_l1_gradient_blocks": (_i, [_i64]),
     "mau_l1_gradient_loss": (_i, [_p, _p, _p, _p, _p, _f, _f, _i, _i, _i, _i, _p]),
