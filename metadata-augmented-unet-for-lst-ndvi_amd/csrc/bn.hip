@@ -42,10 +42,8 @@ __device__ __forceinline__ void ordered_group(int& k, int end, Load load, double
 template <typename Load>
 __device__ __forceinline__ void ordered_pair_sum(int first, int end, Load load, double& s0, double& s1) {
   int k = first;
-#ifndef MAU_REDUCE_SERIAL           // A/B (scripts/build_variants.sh): the plain loop alone
   ordered_group<16>(k, end, load, s0, s1);
   ordered_group<4>(k, end, load, s0, s1);
-#endif
   for (; k + 4 < end; k += 8) {
     s0 += load(k);
     s1 += load(k + 4);

@@ -394,11 +394,9 @@ __device__ __forceinline__ void head_dz(const float* __restrict__ out, const flo
 
 // ---- head: backward pass 1.  One workgroup = BWD_PIX_PER_BLOCK pixels x all C <= 64 channels: BatchNorm partial sums (slab row
 // as bn_relu_bwd_reduce_kernel) and the head's dW / db partials (slab row as head_bwd_kernel) in one pass over y ----
-#ifndef MAU_HEAD_WAVES
-#define MAU_HEAD_WAVES 3          // 168 registers instead of 170: three waves per SIMD instead of two
-#endif
+constexpr int HEAD_WAVES = 3;     // 168 registers instead of 170: three waves per SIMD instead of two
 template <typename T, int MC, bool EX>
-__global__ __launch_bounds__(256, MAU_HEAD_WAVES) void head_bn_bwd_reduce_kernel(const T* __restrict__ y, int ldy, const float* __restrict__ scale,
+__global__ __launch_bounds__(256, HEAD_WAVES) void head_bn_bwd_reduce_kernel(const T* __restrict__ y, int ldy, const float* __restrict__ scale,
                                                                  const float* __restrict__ shift, const float* __restrict__ mean,
                                                                  const float* __restrict__ invstd, const float* __restrict__ w,
                                                                  const float* __restrict__ out, const float* __restrict__ dout,

@@ -24,7 +24,6 @@
 //
 // Replaces nn.Conv2d(.,.,3,padding=1) + the statistics half of nn.BatchNorm2d of VGGBlock
 // (reference src/model.py:12-15), torch.cat([skip, up]) (:279-282) and fuse_embeddings (:248-259).
-#include <stdlib.h>
 #include "igemm_bf16_util.h"
 
 namespace mau {
@@ -61,12 +60,8 @@ struct StageSched {
   static constexpr int NG = 3, ROWS = 2 * MT + 1;
   static constexpr int NM = 18 * MT;                    // MFMAs of a stage
   static constexpr int NR = NG * (ROWS + 6);            // fragment reads of a stage
-#ifdef MAU_CONV_LEAD
-  static constexpr int LEAD = MAU_CONV_LEAD, RING = MAU_CONV_RING, BRING = MAU_CONV_BRING;
-#else
   static constexpr int LEAD = 8;                        // MFMAs between a fragment's read and its first use
   static constexpr int RING = 6, BRING = 10;            // pixel / weight fragment registers (rings in read order)
-#endif
   struct MF { int g, r, mt, dy, nt, ka, kb; };          // ka / kb: read index of its pixel / weight fragment
   struct RD { int isA, g, r, dy, nt, need, last, iss, seq; };   // need / last: first / last MFMA using it; iss: issued after MFMA iss (-1: stage head)
   MF mf[NM] = {};
@@ -142,11 +137,7 @@ __device__ __forceinline__ void mfma32k(const bf16x8& a, const bf16x8& b, f32x4v
 struct PairSched {
   static constexpr int NS = 9, NM = NS * 32, NR = NS * 12;
   static constexpr int B1 = 127, B2 = 159;              // barriers follow these MFMAs (end of stage A's pairs; end of the cross step)
-#ifdef MAU_CONV_M16_LEAD
-  static constexpr int LEAD = MAU_CONV_M16_LEAD, RA = MAU_CONV_M16_RA, RB = MAU_CONV_M16_RB;
-#else
   static constexpr int LEAD = 12, RA = 6, RB = 8;
-#endif
   struct RD { int isA, s, idx, need, last, iss, seq; };   // idx: pixel row y (A) / channel tile n (B)
   RD rd[NR] = {};
   int lo[NM + 1] = {};
@@ -194,8 +185,7 @@ inline constexpr StageSched<MT> kStageSched{};
 // MAU_CONV_KG=0 switches it off (the A/B and test switch).
 constexpr bool has_k_groups(int bn, int mt, int nw) { return bn == 64 && nw == 4 && mt <= 2; }
 static inline bool k_groups_rule(int nChunks, int nItems) {
-  static const bool kg_on = getenv("MAU_CONV_KG") == nullptr || atoi(getenv("MAU_CONV_KG")) != 0;
-  return kg_on && nChunks % 2 == 0 && nChunks >= 4 && nItems <= device_shape().cus;
+  return test_hooks().conv_kg && nChunks % 2 == 0 && nChunks >= 4 && nItems <= device_shape().cus;
 }
 
 // One (pixel tile, cout tile) work item.
@@ -266,19 +256,13 @@ __device__ __forceinline__ void dma_issue(const LoaderArgs la, unsigned long lon
   const bool valid = off32 >= 0;
   unsigned long long pt = ub + 2ull * ((unsigned long long)(unsigned)off32 * um + (unsigned long long)add);
   unsigned long long pe = embn_a + 2ull * (unsigned long long)(long long)(c - la.Ctot);
-#ifndef MAU_CONV_BRANCHY_LOADER
   // both candidates are materialised unconditionally: left to itself the compiler sinks the 64-bit multiply-add into an
   // exec-masked branch per DMA (s_and_saveexec + s_cbranch_execz in the middle of the MFMA stream)
   asm volatile("" : "+v"(pt), "+v"(pe));
-#endif
   const bool is_t = valid & (c < ulim);
   const bool is_e = valid & halo & ((unsigned)(c - la.Ctot) < (unsigned)la.E);
   const unsigned long long src = is_t ? pt : (is_e ? pe : la.zero_a);
-#ifdef MAU_CONV_ABL_ADDRONLY        // timing-only: the address arithmetic without the transfer
-  asm volatile("" ::"v"(src), "v"(lds_dst));
-#else
   __builtin_amdgcn_global_load_lds((glb_ptr)src, (lds_ptr)lds_dst, 16, 0, 0);
-#endif
 }
 
 // timing-only ablations (scripts/build_variants.sh): results are garbage, the instruction streams are what is measured
@@ -287,47 +271,6 @@ constexpr bool ABL_NODMA = true;
 #else
 constexpr bool ABL_NODMA = false;
 #endif
-#ifdef MAU_CONV_ABL_NOWDMA          // timing-only: the weight slabs are never moved (what weights resident in LDS would save at most)
-constexpr bool ABL_NOWDMA = true;
-#else
-constexpr bool ABL_NOWDMA = false;
-#endif
-// TIMING-ONLY probe (round 6; never in the product build): what "BatchNorm-apply + ReLU fused into the consumer's load" would cost with
-// THIS loader -- an LDS-DMA has no register stage, so the affine map + ReLU would have to run as a fix-up pass over the halo image in
-// LDS between "the stage has landed" and "its fragments are read": every wave rewrites its share of the (TH + 2) x 18 pixels x 16
-// channels (16-byte vectors: read, unpack, fma, max, pack, write; all-zero vectors -- the padding ring -- stay zero), then one more
-// workgroup barrier per stage.  Coefficients are register constants here (a real kernel reloads 32 of them per stage): a LOWER bound.
-// Results are garbage (relu of the input); scripts/archive/r6_c5.sh times it.  EXPERIMENTS.md "Round 6", DESIGN.md section 8.
-#ifdef MAU_CONV_PROBE_LDSFIX
-constexpr bool PROBE_LDSFIX = true;
-#else
-constexpr bool PROBE_LDSFIX = false;
-#endif
-template <int VECS, int THREADS, bool F16>
-__device__ __forceinline__ void probe_lds_fix(unsigned buf, int tid, float sc, float sh) {
-#pragma unroll
-  for (int it = 0; it < (VECS + THREADS - 1) / THREADS; ++it) {
-    const int v = tid + it * THREADS;
-    if (v < VECS) {
-      const unsigned a = buf + (unsigned)v * 16u;
-      u32x4 r = lds_read_u128<0>(a);
-      asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(r));
-      const bool keep = (r[0] | r[1] | r[2] | r[3]) != 0u;
-      u32x4 o;
-#pragma unroll
-      for (int d = 0; d < 4; ++d) {
-        f32x2 x = {__uint_as_float(r[d] << 16), __uint_as_float(r[d] & 0xffff0000u)};
-        x = __builtin_elementwise_fma(x, f32x2{sc, sc}, f32x2{sh, sh});
-        x = f32x2{fmaxf(x[0], 0.f), fmaxf(x[1], 0.f)};
-        o[d] = keep ? pack_lp2<F16>(x) : 0u;
-      }
-      asm volatile("ds_write_b128 %0, %1" ::"v"(a), "v"(o) : "memory");
-    }
-  }
-  asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-  __builtin_amdgcn_s_barrier();
-}
-
 // The same wave-DMA through a buffer resource: address = base (SGPR resource) + soff (SGPR: the stage's channel / slab
 // offset) + voff (per lane, constant over the stages of an item); a lane whose voff is 0xffffffff is out of range and
 // receives zeros (hardware range check: the zero padding of the convolution and of the slot grid, no zero page).  One
@@ -335,11 +278,7 @@ __device__ __forceinline__ void probe_lds_fix(unsigned buf, int tid, float sc, f
 // instructions cost clock, not only issue slots ("the clock is the bound").
 typedef __attribute__((address_space(3))) void* lds_vptr;
 __device__ __forceinline__ void dma_issue_buf(__amdgpu_buffer_rsrc_t rs, int voff, int soff, unsigned char* lds_dst) {
-#ifdef MAU_CONV_ABL_ADDRONLY
-  asm volatile("" ::"v"(voff), "s"(soff), "v"(lds_dst));
-#else
   __builtin_amdgcn_raw_ptr_buffer_load_lds(rs, (lds_vptr)lds_dst, 16, voff, soff, 0, 0);
-#endif
 }
 
 // ONE: the layer reads ONE tensor (no second source, no broadcast embedding) -- every data gradient and all but five forward launches
@@ -365,9 +304,6 @@ __global__ __launch_bounds__(NW * KG * 64, 2) void conv3x3_bf16_kernel(ConvP p, 
   const int kg = KG == 1 ? 0 : wave_all / NW;          // K group of this wave; `wave` is its index INSIDE the group everywhere below
   const int wave = KG == 1 ? wave_all : wave_all % NW;
   unsigned char* const smem = smem_all + kg * (2 * STAGE);
-#ifdef MAU_CONV_SETPRIO      // experiment (MI355X_MICROARCH.md, two waves per SIMD, item 4): static priority for the second-dispatched half
-  if (NW == 8 && wave >= 4) __builtin_amdgcn_s_setprio(1);
-#endif
   const int wm = wave % WM, wn = wave / WM;
   const int i32 = perm32(lane & 31), h = lane >> 5;   // tile row (pixel / channel) this lane's operands come from
 
@@ -526,7 +462,7 @@ __global__ __launch_bounds__(NW * KG * 64, 2) void conv3x3_bf16_kernel(ConvP p, 
     unsigned char* dst_ = smem + (STAGE_) * STAGE + (wave + (J) * NW) * 1024;                                        \
     const int c0_ = (CHUNK_) * KC;                                                                                     \
     if ((J) >= HJ || wave + (J) * NW >= HALO_Q) {                                                                      \
-      if (!ABL_NOWDMA) dma_issue_buf(rs_w, off32[(J)], (CHUNK_) * w_stage_bytes32, dst_);                             \
+      dma_issue_buf(rs_w, off32[(J)], (CHUNK_) * w_stage_bytes32, dst_);                                             \
     } else if constexpr (FAST) {                                                                                       \
       if constexpr ((J) < HJ) {                                                                                        \
         if constexpr (ONE) dma_issue_buf(rs_x, off32[(J)], 2 * c0_, dst_);                                           \
@@ -614,11 +550,6 @@ __global__ __launch_bounds__(NW * KG * 64, 2) void conv3x3_bf16_kernel(ConvP p, 
         const bool moreB = chunk + 2 < p.nChunks;
         const int fchunkB = moreB ? chunk + 2 : 0;
         const unsigned sA = lds0 + stage * STAGE, sB = lds0 + (stage ^ 1) * STAGE;
-        if constexpr (PROBE_LDSFIX) {                           // (timing probe: stage A's halo image, published by the barrier above)
-          float psc = 1.0009765625f, psh = 0.0009765625f;
-          asm volatile("" : "+v"(psc), "+v"(psh));
-          probe_lds_fix<HPIX * 2, NW * 64, F16>(sA, tid, psc, psh);
-        }
         bf16x8 fa[PS::RA] = {}, fb[PS::RB] = {};
         unsigned aAddr = 0, bAddr = 0;
         auto issue_read = [&](auto kc) {
@@ -655,11 +586,6 @@ __global__ __launch_bounds__(NW * KG * 64, 2) void conv3x3_bf16_kernel(ConvP p, 
             wait_vmcnt<0>();
 #endif
             __builtin_amdgcn_s_barrier();
-            if constexpr (PROBE_LDSFIX) {                         // (timing probe: stage B's halo image, just published)
-              float psc = 1.0009765625f, psh = 0.0009765625f;
-              asm volatile("" : "+v"(psc), "+v"(psh));
-              probe_lds_fix<HPIX * 2, NW * 64, F16>(sB, tid, psc, psh);
-            }
           }
           if constexpr (M == PS::B2) {                              // stage A's buffer: everyone is done reading it
             __builtin_amdgcn_s_barrier();
@@ -701,11 +627,7 @@ __global__ __launch_bounds__(NW * KG * 64, 2) void conv3x3_bf16_kernel(ConvP p, 
       const unsigned sbase = lds0 + stage * STAGE;
       const unsigned b0a = sbase + boff0, b1a = sbase + boff1;
       const unsigned aa[3] = {sbase + abase[0], sbase + abase[1], sbase + abase[2]};
-#ifdef MAU_CONV_DMA_PER_TAP
-      constexpr int DPT = MAU_CONV_DMA_PER_TAP;
-#else
       constexpr int DPT = PER_WAVE > 9 ? 2 : 1;
-#endif
       // The stage's NM MFMAs in StageSched order; between two MFMAs of the wave (an MFMA holds the vector issue port for
       // 8 of its 32 cycles) go the fragment reads that are LEAD MFMAs from their first use and, every NM / 9 MFMAs, one
       // wave-DMA of the following stage (a wave-DMA costs its issuing wave 60-185 cycles, MI355X_MICROARCH.md: in a burst
@@ -1157,7 +1079,7 @@ static inline TilingId pick_variant(int CoutPad, int N, int H, int W, int Cin) {
   // query) and so counts the rows of <64,4,4>: 4 * ceil(H/32) per tile column and image.  <64,4,8> writes 8 * ceil(H/64), which is the
   // same number only while ceil(H/32) is even -- the K rule applies to those heights alone (H = 256, 250: the measured ones); at any
   // other height <64,4,4> runs whatever Cin is.  launch_conv_bf16_v2 refuses a slab whose row count differs from the query's.
-  static const int l0 = getenv("MAU_CONV_L0") ? atoi(getenv("MAU_CONV_L0")) : -1;      // test hook: 0 / 1 force <64,4,8> / <64,4,4> in the query and the launch alike (both forms stay under the exact big-tile tests)
+  const int l0 = test_hooks().conv_l0;      // MAU_CONV_L0 = 0 / 1 force <64,4,8> / <64,4,4> in the query and the launch alike (both forms stay under the exact big-tile tests)
   if (!wide && best == T64_4_8 && (l0 < 0 ? Cin <= 192 || ceil_div(H, 32) % 2 != 0 : l0 != 0)) best = T64_4_4;
   return best;
 }
@@ -1203,8 +1125,7 @@ static inline ConvPlan make_plan(int N, int H, int W, int Cin, int CoutPad, int 
   if (pl.grid > pl.nItems) pl.grid = pl.nItems;
   // the 16x16x32 loop walks stages in pairs: big-tile variants, buffer-addressed loader, an even number of stages
   // (MAU_CONV_M16=0: the 32x32x16 loop everywhere -- the exact big-tile tests run both loops on the production tilings)
-  static const bool m16 = getenv("MAU_CONV_M16") == nullptr || atoi(getenv("MAU_CONV_M16")) != 0;
-  if (t.mt == 4 && m16 && fast && pl.nChunks % 2 == 0) {
+  if (t.mt == 4 && test_hooks().conv_m16 && fast && pl.nChunks % 2 == 0) {
     pl.form = one_source ? LOOP_PAIR_ONE : LOOP_PAIR;
   } else if (has_k_groups(t.bn, t.mt, t.nw) && epi != EPI_STATS && fast && k_groups_rule(pl.nChunks, pl.nItems)) {
     // Two K groups per workgroup where the layer leaves every CU at most ONE 4-wave workgroup (single-tile inference at the deep

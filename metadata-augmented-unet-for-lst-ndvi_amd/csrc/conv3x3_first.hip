@@ -63,14 +63,10 @@ __device__ __forceinline__ u32x4 pack8(const float (&v)[8]) {
 // the channel (inside a 64-channel output tile) of accumulator register r of A-tile t for lane group q: two runs of 8 per lane
 __device__ __forceinline__ int chan_of(int t, int q, int r) { return 32 * (t >> 1) + 8 * q + 4 * (t & 1) + r; }
 
-#ifndef MAU_FIRST_UNROLL
-#define MAU_FIRST_UNROLL 2           // pixel groups per trip of the inner loop: one group's LDS round trips and MFMA chain beside the other's VALU
-#endif
-#ifndef MAU_FIRST_WAVES
-#define MAU_FIRST_WAVES 2            // waves per SIMD = 4-wave workgroups per CU the register allocation is held to
-#endif
+constexpr int FIRST_UNROLL = 2;      // pixel groups per trip of the inner loop: one group's LDS round trips and MFMA chain beside the other's VALU
+constexpr int FIRST_WAVES = 2;       // waves per SIMD = 4-wave workgroups per CU the register allocation is held to
 template <bool F16, int EPI>
-__global__ __launch_bounds__(NT, MAU_FIRST_WAVES) void first_fwd_kernel(P p) {
+__global__ __launch_bounds__(NT, FIRST_WAVES) void first_fwd_kernel(P p) {
   __shared__ __attribute__((aligned(16))) unsigned char halo[HPIX * 16];
   __shared__ float red[NWAVE][2 * 64];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -203,25 +199,15 @@ __global__ __launch_bounds__(NT, MAU_FIRST_WAVES) void first_fwd_kernel(P p) {
     }
   };
   static_assert(LOADS == 5, "halo pixels per thread");
-#ifdef MAU_FIRST_PREFETCH
-  if ((int)blockIdx.x < p.nTiles) fetch(blockIdx.x);
-#endif
   for (int item = blockIdx.x; item < p.nTiles; item += gridDim.x) {
     int img, ty0, tx0;
     coords(item, img, ty0, tx0);
     __syncthreads();                                     // everyone is done multiplying from the previous tile
-#ifndef MAU_FIRST_NOLOAD             // timing-only ablation: stale LDS
-#ifndef MAU_FIRST_PREFETCH
-    fetch(item);
-#endif
-    commit(item);
-#endif
-    __syncthreads();
-#if defined(MAU_FIRST_PREFETCH) && !defined(MAU_FIRST_NOLOAD)
     // (measured: prefetching the next tile's planes into registers across the multiply phase -- 40 more live registers -- changes nothing:
-    //  the multiply phase, not the load phase, is what the kernel's time is made of; off by default)
-    if (item + (int)gridDim.x < p.nTiles) fetch(item + gridDim.x);
-#endif
+    //  the multiply phase, not the load phase, is what the kernel's time is made of)
+    fetch(item);
+    commit(item);
+    __syncthreads();
     // ---- multiply: a wave owns 4 tile rows = 16 groups of 16 pixels.  Everything a group needs is (wave-uniform scalar) + (per-lane
     // constant): LDS address = lane_lds[s] + row / column offset; store address = uniform row pointer + off1 / off2.  Interior tiles
     // (FULL, the common case) carry no validity masks. ----
@@ -233,7 +219,7 @@ __global__ __launch_bounds__(NT, MAU_FIRST_WAVES) void first_fwd_kernel(P p) {
         const int ry = wv * 4 + rr, gy = ty0 + ry;
         unsigned char* const rowp = yb + (((size_t)img * p.H + gy) * p.W + tx0) * p.ldy * 2;       // (uniform)
         const bool yok = FULL || gy < p.H;
-#pragma unroll MAU_FIRST_UNROLL
+#pragma unroll FIRST_UNROLL
         for (int gc = 0; gc < 4; ++gc) {
           const int cx = gc * 16;
           const unsigned la = (unsigned)((ry * HC + cx) * 16);
@@ -274,12 +260,8 @@ __global__ __launch_bounds__(NT, MAU_FIRST_WAVES) void first_fwd_kernel(P p) {
           unsigned char* const base = rowp + (size_t)cx * p.ldy * 2;
           const int gx1 = tx0 + cx + (n & 7);
           const bool ok1 = st1 && (FULL || (yok && gx1 < p.W)), ok2 = st2 && (FULL || (yok && gx1 + 8 < p.W));
-#if defined(MAU_FIRST_NOSTORE)        // timing-only ablation (scripts/build_variants.sh): what the stores cost
-          if (d1[0] + d2[1] == 0x12345678u) *reinterpret_cast<u32x4*>(base + off1) = d1;
-#else
           if (ok1) __builtin_nontemporal_store(d1, reinterpret_cast<u32x4*>(base + off1));
           if (ok2) __builtin_nontemporal_store(d2, reinterpret_cast<u32x4*>(base + off2));
-#endif
         }
       }
     };
@@ -312,7 +294,7 @@ __global__ __launch_bounds__(NT, MAU_FIRST_WAVES) void first_fwd_kernel(P p) {
   }
 }
 
-static int grid_x(int nTiles, int per_cu = MAU_FIRST_WAVES) {
+static int grid_x(int nTiles, int per_cu = FIRST_WAVES) {
   const int cap = device_shape().cus * per_cu;           // persistent: as many 4-wave workgroups as are resident at once
   return nTiles < cap ? nTiles : cap;
 }

@@ -2,7 +2,8 @@
 //     dW[tap][co][ci] = sum over pixels  dY[pix][co] * X[pix + tap][ci]            (9 GEMMs, M = co, N = ci, K = pixels)
 //
 // Same split-K structure, LDS-DMA staging, transposed fragment reads and slab output as conv3x3_wgrad_bf16.hip (which stays the
-// kernel for images narrower than a 32-pixel tile row); what changes is the MFMA shape and everything that follows from it.
+// kernel for images narrower than a 32-pixel tile row; the shared scaffold is wgrad_common.h, the launch plan of both kernels is in
+// that file); what changes is the MFMA shape and everything that follows from it.
 // Under load the chip holds a higher clock on 16x16x32 than on 32x32x16 at equal cycles per FLOP (MI355X_MICROARCH.md, DVFS
 // give-back (7)); timed in the old kernel's own loop with the operands fed to 16x16x32 MFMAs: -9 % over the U-Net's 18 layers.
 //
@@ -24,13 +25,12 @@
 //
 // Replaces autograd's weight gradient of nn.Conv2d(.,.,3,padding=1) (reference src/model.py:12,14 under loss.backward(),
 // src/train.py:252).
-#include <stdlib.h>
-#include "igemm_bf16_util.h"
+#include "wgrad_common.h"
 
 namespace mau {
 namespace wg3 {
 constexpr int TH = 4, TW = 32, HSP = 48, HROWS = TH + 2, HVAL = TW + 2;
-constexpr int BCI = 64, XROW = BCI * 2;                  // 128-byte rows of the X halo image
+constexpr int XROW = wgrad::BCI * 2;                     // 128-byte rows of the X halo image
 constexpr int XGRP = 5;                                  // 8-pixel DMA groups per halo row (pixels 0..39; 34..39 are zeros)
 constexpr int X_Q = HROWS * XGRP;                        // 30 wave-DMAs
 constexpr int X_BYTES = HROWS * HSP * XROW;              // 36864
@@ -38,26 +38,16 @@ constexpr int DEPTH = 2;                                 // X fragment reads run
 
 using igemm::static_for;
 using igemm::wait_vmcnt;
-typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
+using wgrad::BCI;
+using wgrad::Frag;
+using wgrad::tr_read;
+using wgrad::u32x2;
 typedef float f32x4v __attribute__((ext_vector_type(4)));
 
 // swizzle keys (in 32-byte chunks) of pixel row t
 __device__ __forceinline__ int key2(int t) { return ((t >> 1) & 1) | (((t >> 3) & 1) << 1); }      // 128-byte rows
 __device__ __forceinline__ int key3(int t) { return (t & 3) | (((t >> 3) & 1) << 2); }             // 256-byte rows
 
-struct Frag {
-  u32x4 v;
-};
-template <int OFF, int HI>
-__device__ __forceinline__ void tr_read(Frag& f, unsigned addr) {
-  static_assert(OFF >= 0 && OFF + HI < 65536, "ds offset field");
-  u32x2 lo, hi;
-  asm volatile("ds_read_b64_tr_b16 %0, %2 offset:%3\n\tds_read_b64_tr_b16 %1, %2 offset:%4"
-               : "=&v"(lo), "=&v"(hi)       // early-clobber: the second read still needs the address register (conv3x3_first.hip tr_frag)
-               : "v"(addr), "n"(OFF), "n"(OFF + HI));
-  f.v = __builtin_shufflevector(lo, hi, 0, 1, 2, 3);
-}
 template <int N>
 __device__ __forceinline__ void land1(Frag& a) {
   asm volatile("s_waitcnt lgkmcnt(%1)" : "+v"(a.v) : "n"(N));
@@ -126,30 +116,9 @@ __global__ __launch_bounds__((BCO / 64) * 4 * KG * 64) void wgrad16_kernel(Wgrad
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int wcoh = wave % WCO, wci = (wave / WCO) & 3, kg = wave / (4 * WCO);
-  // ---- work item (see conv3x3_wgrad_bf16.hip): XCD k owns the splits = k (mod 8) and walks their tiles in order ----
+  // ---- work item: (pixel split, co tile, ci tile) from the 1-D workgroup id (wgrad_common.h) ----
   int split, tile_id;
-  {
-    const int nCo = p.CoutPad / BCO, tilesOut = nCo * (p.CinPad / BCI);
-    const int id = blockIdx.x;
-    if (xcd_shift > 0) {
-      const int k = id & ((1 << xcd_shift) - 1), j = id >> xcd_shift;
-      tile_id = j % tilesOut;
-      split = ((j / tilesOut) << xcd_shift) + k;
-    } else if (xcd_shift < 0) {
-      // any other split count: the (split, tile) list in split-major order is cut into one contiguous run per XCD -- the tiles of a
-      // split are still resident on one XCD (two at a run boundary) at about the same time.  The grid is rounded up to a whole number
-      // of workgroups per XCD; the (at most XCDs - 1) surplus workgroups leave here, before any barrier.
-      const int sh = -xcd_shift, k = id & ((1 << sh) - 1), j = id >> sh;
-      const int total = nsplit * tilesOut, per = (total + (1 << sh) - 1) >> sh;
-      const int w = k * per + j;
-      if (w >= total) return;
-      split = w / tilesOut;
-      tile_id = w - split * tilesOut;
-    } else {
-      split = id % nsplit;
-      tile_id = id / nsplit;
-    }
-  }
+  if (!wgrad::work_item(blockIdx.x, nsplit, xcd_shift, (p.CoutPad / BCO) * (p.CinPad / BCI), split, tile_id)) return;
   const int co0 = (tile_id % (p.CoutPad / BCO)) * BCO, ci0 = (tile_id / (p.CoutPad / BCO)) * BCI;
   // ---- the X source of this workgroup's 64 input channels: tensor x | tensor x1 (virtual concat) | broadcast embedding.  The
   // launcher guarantees that the block lies inside ONE source (C0 and C0 + C1 on 64-channel boundaries where a next source follows).
@@ -274,22 +243,12 @@ __global__ __launch_bounds__((BCO / 64) * 4 * KG * 64) void wgrad16_kernel(Wgrad
     for (int c = 0; c < 4; ++c) acc[t][c] = f32x4v{0.f, 0.f, 0.f, 0.f};
 
   // ---- split-K: this workgroup's pixel tiles ----
-  const int per = (p.nTiles + nsplit - 1) / nsplit;
-  const int t0 = split * per, t1 = min(p.nTiles, t0 + per);
+  int t0, t1;
+  wgrad::split_range(split, nsplit, p.nTiles, t0, t1);
   if (t0 < t1) {
-    int lcur = t0, ltx = t0 % p.tilesX, lty = (t0 / p.tilesX) % p.tilesY, ln = t0 / (p.tilesX * p.tilesY);
-    auto advance = [&]() {
-      if (lcur + 1 < t1) {
-        ++lcur;
-        if (++ltx == p.tilesX) {
-          ltx = 0;
-          if (++lty == p.tilesY) {
-            lty = 0;
-            ++ln;
-          }
-        }
-      }
-    };
+    int lcur, ltx, lty, ln;                            // the tile being loaded (wgrad_common.h)
+    wgrad::first_tile(t0, p.tilesX, p.tilesY, lcur, ltx, lty, ln);
+    auto advance = [&]() { wgrad::advance(lcur, ltx, lty, ln, t1, p.tilesX, p.tilesY); };
     static_for<0, PER_WAVE>([&](auto jc) { issue_slot(jc, 0, ln, lty * TH, ltx * TW); });
     int stage = 0;
     for (int tile = t0; tile < t1; ++tile) {
@@ -370,28 +329,9 @@ __global__ __launch_bounds__((BCO / 64) * 4 * KG * 64) void wgrad16_kernel(Wgrad
   if constexpr (KG == 2) {
     // ---- the two wave groups add their accumulators through LDS (fixed order: group 0 + group 1), 3 taps per round ----
     __builtin_amdgcn_s_barrier();
-    float* red = reinterpret_cast<float*>(smem) + (size_t)(wave % (NW / 2)) * (3 * 16 * 64);
+    float* red = reinterpret_cast<float*>(smem) + (size_t)(wave % (NW / 2)) * wgrad::hand_over_floats;
 #pragma unroll
-    for (int round = 0; round < 3; ++round) {
-      if (kg == 1) {
-#pragma unroll
-        for (int t = 0; t < 3; ++t)
-#pragma unroll
-          for (int c = 0; c < 4; ++c)
-#pragma unroll
-            for (int r = 0; r < 4; ++r) red[((t * 4 + c) * 4 + r) * 64 + lane] = acc[round * 3 + t][c][r];
-      }
-      __syncthreads();
-      if (kg == 0) {
-#pragma unroll
-        for (int t = 0; t < 3; ++t)
-#pragma unroll
-          for (int c = 0; c < 4; ++c)
-#pragma unroll
-            for (int r = 0; r < 4; ++r) acc[round * 3 + t][c][r] += red[((t * 4 + c) * 4 + r) * 64 + lane];
-      }
-      __syncthreads();
-    }
+    for (int round = 0; round < 3; ++round) wgrad::wave_groups_round(reinterpret_cast<float(&)[9][16]>(acc), red, round, kg, lane);   // ([tap][co tile][register] = 16 floats per tap)
     if (kg != 0) return;
   }
   // ---- partial slab [split][tap][CoutPad][CinPad]; C/D of 16x16: column (ci) = lane % 16, row (co) = 4 (lane / 16) + register ----
@@ -411,12 +351,7 @@ template <int BCO, int KG, bool F16, bool MIXED>
 static int launch(const WgradP& p, const WgPlan& pl, hipStream_t st) {
   constexpr int NW = (BCO / 64) * 4 * KG;
   constexpr size_t stage = (size_t)(TH * TW * BCO * 2) + X_BYTES;
-  constexpr size_t red = KG == 2 ? (size_t)(NW / 2) * 3 * 16 * 64 * sizeof(float) : 0;
-  constexpr size_t lds = 2 * stage > red ? 2 * stage : red;
-  static_assert(lds <= 160 * 1024, "LDS budget");
-  MAU_LDS_ATTR(lds, &wgrad16_kernel<BCO, KG, F16, MIXED>);
-  MAU_LAUNCH((wgrad16_kernel<BCO, KG, F16, MIXED>), dim3(pl.grid), dim3(NW * 64), lds, st, p, pl.nsplit, pl.xcd_shift);
-  return check_launch("wgrad16_kernel");
+  return wgrad::launch<&wgrad16_kernel<BCO, KG, F16, MIXED>, 2 * stage, NW, KG>("wgrad16_kernel", p, pl, st);
 }
 }  // namespace wg3
 

@@ -20,8 +20,10 @@
 //               whole stage earlier), then the next stage's wave-DMAs are issued one per step from the head of
 //               the stage, between the MFMA groups, with select-only (branch-free) source addressing: they stay
 //               in flight while the current stage multiplies, and no wait on the vector-memory counter sits
-//               between their issue and the MFMAs.  (A third stage, template NS, bought nothing once the DMAs
-//               were issued at the head.)
+//               between their issue and the MFMAs.  (A third stage bought nothing once the DMAs were issued at the
+//               head; the kernel has exactly two.)
+//   scaffold  : the work-item order, the split-K tile cursor, the fragment read, the hand-over between the two wave
+//               groups and the launch are shared with conv3x3_wgrad16.hip: wgrad_common.h
 //   reduction : every workgroup owns a pixel range (split-K) and writes its partial with plain
 //               coalesced stores into slab [split][9][Cout64][Cin64]; the splits are summed in
 //               fixed order by the unpack kernel -> bitwise reproducible, no float atomics
@@ -31,47 +33,27 @@
 //
 // Replaces autograd's weight gradient of nn.Conv2d(.,.,3,padding=1) (reference src/model.py:12,14
 // under loss.backward(), src/train.py:252).
-#include <stdlib.h>
-#include "igemm_bf16_util.h"
+#include "wgrad_common.h"
 
 namespace mau {
 
 namespace wg2 {
 constexpr int TH = 8, TW = 16, HW_ = TW + 2, HALO = (TH + 2) * (TW + 2);   // 180
-constexpr int BCI = 64;
-constexpr int XROW = BCI * 2;                       // 128-byte rows of the X halo image
-#ifndef WG_DEPTH
-#define WG_DEPTH 2
-#endif
-constexpr int DEPTH = WG_DEPTH;                     // fragment reads run this many steps ahead of their MFMAs
+constexpr int XROW = wgrad::BCI * 2;                // 128-byte rows of the X halo image
+constexpr int DEPTH = 2;                            // fragment reads run this many steps ahead of their MFMAs
 
 using igemm::glb_ptr;
 using igemm::lds_ptr;
 using igemm::static_for;
 using igemm::wait_vmcnt;
-typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
+using wgrad::BCI;
+using wgrad::Frag;
+using wgrad::tr_read;
 
 // chunk swizzles (16-byte chunks): 4 consecutive rows x 64 bytes must cover all 64 banks
 __device__ __forceinline__ int swz128(int row) { return ((row >> 1) & 1) << 2; }   // 128-byte rows
 __device__ __forceinline__ int swz256(int row) { return (row & 3) << 2; }          // 256-byte rows
 
-// one k16 operand fragment = two transposed 8-byte reads (k 0..3 | 4..7 of the lane half's 8 pixels), joined into the
-// MFMA's 4-register operand AT THE READ: joined later (after the counted wait had taken the two halves as separate
-// in/out operands) the halves lived in unrelated register pairs and every fragment cost 2-4 v_mov -- 97 copies per stage
-// next to 72 MFMAs, in a kernel whose clock falls with every vector instruction.
-struct Frag {
-  u32x4 v;
-};
-template <int OFF, int HI>
-__device__ __forceinline__ void tr_read(Frag& f, unsigned addr) {
-  static_assert(OFF >= 0 && OFF + HI < 65536, "ds offset field");
-  u32x2 lo, hi;
-  asm volatile("ds_read_b64_tr_b16 %0, %2 offset:%3\n\tds_read_b64_tr_b16 %1, %2 offset:%4"
-               : "=&v"(lo), "=&v"(hi)       // early-clobber: the second read still needs the address register (conv3x3_first.hip tr_frag)
-               : "v"(addr), "n"(OFF), "n"(OFF + HI));
-  f.v = __builtin_shufflevector(lo, hi, 0, 1, 2, 3);
-}
 // wait until at most N of this wave's LDS operations are outstanding; re-defines the fragments about to be
 // consumed so that their MFMAs cannot be scheduled above the wait
 template <int N>
@@ -80,14 +62,6 @@ __device__ __forceinline__ void land(Frag& a, Frag& b) {
 }
 template <bool F16>
 __device__ __forceinline__ f32x16 mfma_frag(const Frag& a, const Frag& b, f32x16 c) {
-#ifdef WG_HACK16        // TIMING ONLY (garbage results): the same operands through two v_mfma_f32_16x16x32 on quarters of the accumulator
-  typedef float f32x4v __attribute__((ext_vector_type(4)));
-  f32x4v q0 = {c[0], c[1], c[2], c[3]}, q1 = {c[4], c[5], c[6], c[7]}, q2 = {c[8], c[9], c[10], c[11]}, q3 = {c[12], c[13], c[14], c[15]};
-  q0 = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, a.v), __builtin_bit_cast(bf16x8, b.v), q0, 0, 0, 0);
-  q1 = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, a.v), __builtin_bit_cast(bf16x8, b.v), q1, 0, 0, 0);
-  // (a 32x32x16 MFMA = 16384 MACs = TWO 16x16x32; the other two quarters pass through)
-  return f32x16{q0[0], q0[1], q0[2], q0[3], q1[0], q1[1], q1[2], q1[3], q2[0], q2[1], q2[2], q2[3], q3[0], q3[1], q3[2], q3[3]};
-#endif
   if constexpr (F16) {
     typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
     return __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8, a.v), __builtin_bit_cast(f16x8, b.v), c, 0, 0, 0);
@@ -113,7 +87,7 @@ struct Sched {
 
 // KG = number of wave groups that split the tile rows of every stage between them: KG = 2 gives the
 // 64-channel variant 8 waves (two per SIMD) instead of 4.
-template <int BCO, int KG, bool F16, int NS>
+template <int BCO, int KG, bool F16>
 __global__ __launch_bounds__(BCO * 4 * KG) void wgrad_bf16_kernel(WgradP p, int nsplit, int xcd_shift) {
   constexpr int NW = BCO / 16 * KG;                  // waves: (BCO/32) x 2 x KG
   constexpr int WCO = BCO / 32;
@@ -131,41 +105,15 @@ __global__ __launch_bounds__(BCO * 4 * KG) void wgrad_bf16_kernel(WgradP p, int 
   static_assert(PER_WAVE <= NSTEP, "one DMA per step at most");
   static_assert(ROWS % 2 == 0, "row parity of the halo swizzle");
 
-  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];   // NS * max(STAGE, PER_WAVE * NW KiB)
-  constexpr int STRIDE = PER_WAVE * NW * 1024 > STAGE ? PER_WAVE * NW * 1024 : STAGE;   // stage pitch incl. pad slots
+  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];   // 2 * STRIDE
+  constexpr int STRIDE = PER_WAVE * NW * 1024 > STAGE ? PER_WAVE * NW * 1024 : STAGE;   // stage pitch incl. pad slots (they are written too)
 
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int wco = wave % WCO, wci = (wave / WCO) & 1, kg = wave / (2 * WCO);
-  // ---- work item: (pixel split, co tile, ci tile) from the 1-D workgroup id ----
-  // The workgroups of one split stream the SAME pixels (dY tile shared by the ci tiles, X halo shared by the co tiles).
-  // Hardware deals workgroup ids round-robin over the XCDs (id % 8; speed only): with xcd_shift > 0 (nsplit a multiple of the XCD
-  // count) XCD k owns the splits = k (mod 8) and walks their tiles in order, so all tiles of a split are resident on ONE
-  // XCD at about the same time and its L2 serves the re-reads.  With id = split + nsplit * tile (the other form), a split
-  // count like 85 or 21 scattered the tiles of a split over all XCDs: conv0_1.conv1 read its 268 MB dY three times.
+  // ---- work item: (pixel split, co tile, ci tile) from the 1-D workgroup id (wgrad_common.h) ----
   int split, tile_id;
-  {
-    const int nCo = p.CoutPad / BCO, tilesOut = nCo * (p.CinPad / BCI);
-    const int id = blockIdx.x;
-    if (xcd_shift > 0) {
-      const int k = id & ((1 << xcd_shift) - 1), j = id >> xcd_shift;
-      tile_id = j % tilesOut;
-      split = ((j / tilesOut) << xcd_shift) + k;
-    } else if (xcd_shift < 0) {
-      // any other split count: the (split, tile) list in split-major order is cut into one contiguous run per XCD -- the tiles of a
-      // split are still resident on one XCD (two at a run boundary) at about the same time.  The grid is rounded up to a whole number
-      // of workgroups per XCD; the (at most XCDs - 1) surplus workgroups leave here, before any barrier.
-      const int sh = -xcd_shift, k = id & ((1 << sh) - 1), j = id >> sh;
-      const int total = nsplit * tilesOut, per = (total + (1 << sh) - 1) >> sh;
-      const int w = k * per + j;
-      if (w >= total) return;
-      split = w / tilesOut;
-      tile_id = w - split * tilesOut;
-    } else {
-      split = id % nsplit;
-      tile_id = id / nsplit;
-    }
-  }
+  if (!wgrad::work_item(blockIdx.x, nsplit, xcd_shift, (p.CoutPad / BCO) * (p.CinPad / BCI), split, tile_id)) return;
   const int co0 = (tile_id % (p.CoutPad / BCO)) * BCO, ci0 = (tile_id / (p.CoutPad / BCO)) * BCI;
   const unsigned short* __restrict__ xg = reinterpret_cast<const unsigned short*>(p.x);
   const unsigned short* __restrict__ x1g = reinterpret_cast<const unsigned short*>(p.x1);
@@ -259,35 +207,19 @@ __global__ __launch_bounds__(BCO * 4 * KG) void wgrad_bf16_kernel(WgradP p, int 
   const unsigned lds0 = (unsigned)(size_t)((__attribute__((address_space(3))) unsigned char*)smem);
 
   // ---- split-K: this workgroup's pixel tiles ----
-  const int per = (p.nTiles + nsplit - 1) / nsplit;
-  const int t0 = split * per, t1 = min(p.nTiles, t0 + per);
+  int t0, t1;
+  wgrad::split_range(split, nsplit, p.nTiles, t0, t1);
   if (t0 < t1) {
-    // (n, ty0, tx0) of the tile being LOADED, advanced incrementally (wave-uniform scalars); past the last tile the cursor
-    // stays there: the tile is re-fetched into an idle buffer (nobody reads it), which keeps the DMA count per stage fixed
-    int lcur = t0, ltx = t0 % p.tilesX, lty = (t0 / p.tilesX) % p.tilesY, ln = t0 / (p.tilesX * p.tilesY);
-    auto advance = [&]() {
-      if (lcur + 1 < t1) {
-        ++lcur;
-        if (++ltx == p.tilesX) {
-          ltx = 0;
-          if (++lty == p.tilesY) {
-            lty = 0;
-            ++ln;
-          }
-        }
-      }
-    };
-    static_for<0, NS - 1>([&](auto stc) {
-      constexpr int st = decltype(stc)::value;
-      if constexpr (st > 0) advance();
-      static_for<0, PER_WAVE>([&](auto jc) { issue_slot(jc, st, ln, lty * TH, ltx * TW); });
-    });
+    int lcur, ltx, lty, ln;                            // the tile being loaded (wgrad_common.h)
+    wgrad::first_tile(t0, p.tilesX, p.tilesY, lcur, ltx, lty, ln);
+    auto advance = [&]() { wgrad::advance(lcur, ltx, lty, ln, t1, p.tilesX, p.tilesY); };
+    static_for<0, PER_WAVE>([&](auto jc) { issue_slot(jc, 0, ln, lty * TH, ltx * TW); });
     int stage = 0;
     for (int tile = t0; tile < t1; ++tile) {
-      wait_vmcnt<(NS - 2) * PER_WAVE>();               // this wave's DMAs of the stage about to be multiplied (issued NS - 1 stages ago)
-      __builtin_amdgcn_s_barrier();                    // ... everyone's have landed, and everyone is done reading the buffer refilled next
+      wait_vmcnt<0>();                                 // this wave's DMAs of the stage about to be multiplied (issued a stage ago)
+      __builtin_amdgcn_s_barrier();                    // ... everyone's have landed, and everyone is done reading the other buffer
       advance();
-      const int lstage = stage == 0 ? NS - 1 : stage - 1;   // buffer multiplied in the previous iteration
+      const int lstage = stage == 0 ? 1 : stage - 1;       // the other buffer: multiplied in the previous iteration, refilled now (this form, not stage ^ 1: as the toggle below, it keeps the compiled kernel identical to its measured form -- change both or neither)
       const int nty0 = lty * TH, ntx0 = ltx * TW, nn = ln;
       const unsigned sb = lds0 + stage * STRIDE;
       const unsigned aa = sb + a_off;
@@ -323,7 +255,7 @@ __global__ __launch_bounds__(BCO * 4 * KG) void wgrad_bf16_kernel(WgradP p, int 
           }
         });
       });
-      stage = stage + 1 == NS ? 0 : stage + 1;
+      stage = stage + 1 == 2 ? 0 : stage + 1;            // (this form, not stage ^ 1: with lstage above it keeps the compiled kernel identical to its measured form)
     }
     wait_vmcnt<0>();                                   // the idle re-fetch must land before the LDS is reused / released
   }
@@ -332,24 +264,9 @@ __global__ __launch_bounds__(BCO * 4 * KG) void wgrad_bf16_kernel(WgradP p, int 
   if constexpr (KG == 2) {
     // ---- the two wave groups add their accumulators through LDS (fixed order: group 0 + group 1), 3 taps per round ----
     __builtin_amdgcn_s_barrier();
-    float* red = reinterpret_cast<float*>(smem) + (size_t)(wave % (NW / 2)) * (3 * 16 * 64);
+    float* red = reinterpret_cast<float*>(smem) + (size_t)(wave % (NW / 2)) * wgrad::hand_over_floats;
 #pragma unroll
-    for (int round = 0; round < 3; ++round) {
-      if (kg == 1) {
-#pragma unroll
-        for (int t = 0; t < 3; ++t)
-#pragma unroll
-          for (int r = 0; r < 16; ++r) red[(t * 16 + r) * 64 + lane] = acc[round * 3 + t][r];
-      }
-      __syncthreads();
-      if (kg == 0) {
-#pragma unroll
-        for (int t = 0; t < 3; ++t)
-#pragma unroll
-          for (int r = 0; r < 16; ++r) acc[round * 3 + t][r] += red[(t * 16 + r) * 64 + lane];
-      }
-      __syncthreads();
-    }
+    for (int round = 0; round < 3; ++round) wgrad::wave_groups_round(reinterpret_cast<float(&)[9][16]>(acc), red, round, kg, lane);
     if (kg != 0) return;
   }
   // ---- partial slab: [split][tap][CoutPad][CinPad], 128 contiguous bytes per half-wave ----
@@ -363,6 +280,21 @@ __global__ __launch_bounds__(BCO * 4 * KG) void wgrad_bf16_kernel(WgradP p, int 
     }
 }
 
+template <int BCO, int KG, bool F16>
+static int launch(const WgradP& p, const WgPlan& pl, hipStream_t st) {
+  constexpr int NW = BCO / 16 * KG;
+  constexpr int DY_Q = TH * TW * (BCO / 8) / 64;
+  constexpr int X_Q = (HALO * 8 + 63) / 64;
+  constexpr int PER_WAVE = (DY_Q + X_Q + NW - 1) / NW;
+  constexpr size_t stage = (size_t)(PER_WAVE * NW > DY_Q + X_Q ? PER_WAVE * NW : DY_Q + X_Q) * 1024;
+  return wgrad::launch<&wgrad_bf16_kernel<BCO, KG, F16>, 2 * stage, NW, KG>("wgrad_bf16_kernel", p, pl, st);
+}
+}  // namespace wg2
+
+// ------------------------------------------------------------------------------------------
+// The launch plan of a 16-bit weight gradient, for BOTH kernels (this file's and conv3x3_wgrad16.hip's): which kernel, its pixel
+// tiles, the split count, the work-item order and the grid.  Host code only.
+// ------------------------------------------------------------------------------------------
 // The kernels' work-item order for a split count (speed only: every (split, tile) computes the same slab whatever its workgroup id).
 //   > 0 : XCD k owns the splits = k (mod XCDs) -- split counts that are whole numbers per XCD (round 3);
 //   < 0 : the split-major (split, tile) list is cut into one contiguous run per XCD -- ANY other count (round 6); the grid is rounded
@@ -379,32 +311,15 @@ static inline int wgrad_grid(int nsplit, int tilesOut, int xcd_shift) {
   return xcd_shift < 0 ? (((total + (1 << -xcd_shift) - 1) >> -xcd_shift) << -xcd_shift) : total;
 }
 
-template <int BCO, int KG, bool F16, int NS>
-static int launch(const WgradP& p, const WgPlan& pl, hipStream_t st) {
-  constexpr int NW = BCO / 16 * KG;
-  constexpr int DY_Q = TH * TW * (BCO / 8) / 64;
-  constexpr int X_Q = (HALO * 8 + 63) / 64;
-  constexpr int PER_WAVE = (DY_Q + X_Q + NW - 1) / NW;
-  constexpr size_t stage = (size_t)(PER_WAVE * NW > DY_Q + X_Q ? PER_WAVE * NW : DY_Q + X_Q) * 1024;
-  constexpr size_t red = KG == 2 ? (size_t)(NW / 2) * 3 * 16 * 64 * sizeof(float) : 0;
-  constexpr size_t lds = NS * stage > red ? NS * stage : red;
-  static_assert(lds <= 160 * 1024, "LDS budget");
-  MAU_LDS_ATTR(lds, &wgrad_bf16_kernel<BCO, KG, F16, NS>);
-  MAU_LAUNCH((wgrad_bf16_kernel<BCO, KG, F16, NS>), dim3(pl.grid), dim3(BCO * 4 * KG), lds, st, p, pl.nsplit, pl.xcd_shift);
-  return check_launch("wgrad_bf16_kernel");
-}
-}  // namespace wg2
-
 // Which kernel multiplies a layer: the 16x16x32 kernel (conv3x3_wgrad16.hip) works on 4 x 32 pixel tiles, this file's 32x32x16 kernel on
 // 8 x 16 ones.  The first is ~9 % faster per MFMA (clock), so it takes every layer unless its tiles waste more than that on
-// pixels outside the image (16-pixel-wide bottleneck images: twice the work).  MAU_WGRAD16=0: the 32x32x16 kernel everywhere.
+// pixels outside the image (16-pixel-wide bottleneck images: twice the work).  MAU_WGRAD16=0 (test hook): the 32x32x16 kernel everywhere.
 struct WgVariant {
   bool k16;
   int th, tw;
 };
 static WgVariant wgrad_variant(int H, int W, bool addressable) {
-  const char* e = getenv("MAU_WGRAD16");
-  const bool allow = addressable && (e == nullptr || atoi(e) != 0);
+  const bool allow = addressable && test_hooks().wgrad16;
   const double a16 = (double)ceil_div(H, 4) * 4 * ceil_div(W, 32) * 32, a32 = (double)ceil_div(H, wg2::TH) * wg2::TH * ceil_div(W, wg2::TW) * wg2::TW;
   if (allow && a16 <= 1.08 * a32) return {true, 4, 32};
   return {false, wg2::TH, wg2::TW};
@@ -422,10 +337,7 @@ static int wgrad_splits(int nTiles, bool k16, int CoutPad, int CinPad, int outTi
   if (smax < 1) smax = 1;
   if (smax > 1024) smax = 1024;
   if ((size_t)smax > cap) smax = (int)cap;
-  if (const char* f = getenv("MAU_WGRAD_SPLITS_FORCE")) {      // timing experiments only (read per call): a given split count, clipped
-    const int s = atoi(f);
-    if (s >= 1) return s > smax ? smax : s;
-  }
+  if (const int s = TestHooks::wgrad_splits_force(); s >= 1) return s > smax ? smax : s;   // (test hook: a given split count, clipped)
   // Which split count: a workgroup costs its nTiles / s pixel-tile iterations plus a fixed overhead OV (pipeline fill, the 147-295 KB
   // slab it writes and the second stage reads back), and the launch runs in ceil(workgroups / CUs) rounds:
   //     cost(s) = rounds(s) * (nTiles / s + OV),     OV = 16 iterations of the 4 x 32 tiling, 10 of the 8 x 16 one
@@ -469,8 +381,8 @@ static WgPlan make_wg_plan(int N, int H, int W, int Cout, int Cin, bool addressa
   pl.tilesY = ceil_div(H, v.th);
   pl.nTiles = N * pl.tilesX * pl.tilesY;
   pl.nsplit = wgrad_splits(N * ceil_div(H, vq.th) * ceil_div(W, vq.tw), vq.k16, CoutPad, CinPad, pl.outTiles);
-  pl.xcd_shift = wg2::wgrad_xcd_shift(pl.nsplit);
-  pl.grid = wg2::wgrad_grid(pl.nsplit, pl.outTiles, pl.xcd_shift);
+  pl.xcd_shift = wgrad_xcd_shift(pl.nsplit);
+  pl.grid = wgrad_grid(pl.nsplit, pl.outTiles, pl.xcd_shift);
   pl.mixed = mixed;
   return pl;
 }
@@ -489,11 +401,8 @@ int launch_wgrad_bf16_v2(const WgradP& p, bool f16, hipStream_t st) {
   q.tilesY = pl.tilesY;
   q.nTiles = pl.nTiles;
   if (pl.k16) return launch_wgrad16(q, f16, pl, st);
-#ifndef WG_NS64
-#define WG_NS64 2
-#endif
-  if (pl.bco == 128) return f16 ? wg2::launch<128, 1, true, 2>(q, pl, st) : wg2::launch<128, 1, false, 2>(q, pl, st);
-  return f16 ? wg2::launch<64, 2, true, WG_NS64>(q, pl, st) : wg2::launch<64, 2, false, WG_NS64>(q, pl, st);
+  if (pl.bco == 128) return f16 ? wg2::launch<128, 1, true>(q, pl, st) : wg2::launch<128, 1, false>(q, pl, st);
+  return f16 ? wg2::launch<64, 2, true>(q, pl, st) : wg2::launch<64, 2, false>(q, pl, st);
 }
 
 }  // namespace mau

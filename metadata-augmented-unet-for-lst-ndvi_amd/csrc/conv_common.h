@@ -1,8 +1,32 @@
 // conv_common.h -- declarations shared by the convolution translation units.
 #pragma once
+#include <stdlib.h>
 #include "mau_common.h"
 
 namespace mau {
+
+// Test hooks: the only environment variables the library reads.  They exist for the tests and the A/B scripts, which run both
+// sides of a dispatch rule on the same library; no product path sets them.
+//   MAU_CONV_KG=0    no K-group launches (k_groups_rule)          MAU_CONV_M16=0  the 32x32x16 loop on the big tiles too
+//   MAU_CONV_L0=0|1  force <64,4,8> | <64,4,4> on 64-channel tiles  MAU_WGRAD16=0   the 32x32x16 weight gradient everywhere
+//   MAU_WGRAD_SPLITS_FORCE=s   the weight gradient's split count (clipped by wgrad_splits)
+// The first four are read once per process; the split count is read per call (a test walks several counts in one process).
+// So an A/B of one of the first four needs a process per side: changing os.environ after the first launch does nothing
+// (scripts/wgrad_ab.py flips its variable inside one process -- it can compare split counts only).
+struct TestHooks {
+  bool conv_kg, conv_m16, wgrad16;
+  int conv_l0;                               // -1: the rule decides
+  static int env_int(const char* name, int unset) {
+    const char* e = getenv(name);
+    return e ? atoi(e) : unset;
+  }
+  static int wgrad_splits_force() { return env_int("MAU_WGRAD_SPLITS_FORCE", 0); }   // < 1: the rule decides
+};
+inline const TestHooks& test_hooks() {
+  static const TestHooks h = {TestHooks::env_int("MAU_CONV_KG", 1) != 0, TestHooks::env_int("MAU_CONV_M16", 1) != 0,
+                              TestHooks::env_int("MAU_WGRAD16", 1) != 0, TestHooks::env_int("MAU_CONV_L0", -1)};
+  return h;
+}
 
 // 16 zero bytes in global memory: DMA source of padding pixels / channels (one copy per translation unit)
 static __device__ __attribute__((aligned(16))) unsigned int g_zero_page[4] = {0u, 0u, 0u, 0u};

@@ -32,14 +32,9 @@ typedef float f32x2 __attribute__((ext_vector_type(2)));
 // Gate nonlinearities on the hardware exp / rcp (v_exp_f32, v_rcp_f32: ~1 ulp each): absolute error ~1e-7 per evaluation,
 // which the contractive recurrence does not amplify (G11: 828 steps, embedding and gradients within 1e-4 of the reference);
 // libm's expf / tanhf cost ~100 instructions and 50 branches per call on the critical path of every step.
-#ifdef MAU_LSTM_LIBM
-__device__ __forceinline__ float sigmoidf_(float x) { return 1.f / (1.f + expf(-x)); }
-__device__ __forceinline__ float tanhf_(float x) { return tanhf(x); }
-#else
 // (v_rcp_f32 directly: __frcp_rn expands to a 12-instruction IEEE division)
 __device__ __forceinline__ float sigmoidf_(float x) { return __builtin_amdgcn_rcpf(1.f + __expf(-x)); }
 __device__ __forceinline__ float tanhf_(float x) { return 1.f - 2.f * __builtin_amdgcn_rcpf(1.f + __expf(2.f * x)); }
-#endif
 
 // value of lane (quad base + J) of every quad, for all four lanes of the quad (DPP quad_perm: no LDS, no barrier)
 template <int J>
@@ -109,16 +104,11 @@ __global__ __launch_bounds__(4 * HP) void lstm_fwd_kernel(const float* __restric
       const f32x4 hv = *reinterpret_cast<const f32x4*>(&hq[kk]);
 #pragma unroll
       for (int g = 0; g < 4; ++g) {
-#ifdef MAU_LSTM_PACKED
-        p[g] = __builtin_elementwise_fma(w[g][kk >> 1], hv.xy, p[g]);
-        p[g] = __builtin_elementwise_fma(w[g][(kk >> 1) + 1], hv.zw, p[g]);
-#else
         // scalar FMAs on purpose: a wave64 v_pk_fma_f32 costs more issue cycles than the two v_fma_f32 it replaces
         p[g][0] = fmaf(w[g][kk >> 1][0], hv[0], p[g][0]);
         p[g][1] = fmaf(w[g][kk >> 1][1], hv[1], p[g][1]);
         p[g][0] = fmaf(w[g][(kk >> 1) + 1][0], hv[2], p[g][0]);
         p[g][1] = fmaf(w[g][(kk >> 1) + 1][1], hv[3], p[g][1]);
-#endif
       }
     }
     // gate g's pre-activation = sum over the quad of p[g]; lane q keeps gate q's

@@ -1,7 +1,11 @@
 #!/usr/bin/env python3
 """Same-process A/B of the weight-gradient kernel's work-item order (MAU_WGRAD_XCD=0: id = split + nsplit * tile, any split count;
 1: XCD-contiguous splits, split counts a multiple of the XCD count) over the U-Net's conv shapes (bf16, B=32), interleaved rounds.
-Times the kernel alone and kernel + unpack (the split-K sum's cost depends on the split count)."""
+Times the kernel alone and kernel + unpack (the split-K sum's cost depends on the split count).
+As it stands this script compares NOTHING: it flips AB_VAR in os.environ inside one process, MAU_WGRAD_XCD is no longer read by the
+library, and MAU_WGRAD16 (profiles/r3: AB_VAR=MAU_WGRAD16) is read once per process (conv_common.h, TestHooks), so both sides run the
+same kernel.  Of the library's hooks only MAU_WGRAD_SPLITS_FORCE is read per call.  For MAU_WGRAD16 run one process per side
+(scripts/wg_one.py, or this script twice with the variable set outside and AB_VAR pointing at an unused name)."""
 import os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch

@@ -322,7 +322,8 @@ def test_wgrad16_production_shapes_exact_integers(mau, shape, splits):
 
 @pytest.mark.parametrize("dt", [torch.bfloat16, torch.float16])
 @pytest.mark.parametrize("shape", [(2, 16, 24, 40, 19, 21, 0), (1, 64, 128, 64, 16, 16, 16), (3, 32, 8, 130, 40, 33, 0),
-                                   (2, 128, 64, 72, 70, 50, 8), (1, 16, 5, 8, 9, 7, 0)])
+                                   (2, 128, 64, 72, 70, 50, 8), (1, 16, 5, 8, 9, 7, 0),
+                                   (2, 16, 24, 72, 19, 21, 0)])     # wgrad16_kernel<128,1,*,MIXED>: sources off the 64-channel grid, Cout pads to 128
 def test_conv3x3_two_tensor_sources_bitwise(mau, dt, shape):
     """Virtual channel concat (mau_conv3x3_fwd2 / mau_conv3x3_wgrad2): the convolution over [x | x1 | broadcast(emb)] read
     from two tensors must equal, bit for bit, the convolution over the materialised concatenation (same K order), and
