@@ -10,7 +10,7 @@ In the reference the SSIM values pass through ``torch.Tensor(ssim_vals)`` (:89-9
 term changes the reported number, never the gradient.  ``piq`` (the SSIM provider) is not available in the
 build environment, so the SSIM VALUE follows piq's published default algorithm (11x11 Gaussian, sigma 1.5,
 k1 0.01, k2 0.03, average-pool downsampling by max(1, round(min(H, W)/256))): one fused HIP reduction
-(``mau_ssim_loss``, csrc/ssim.hip), checked on the GPU against the torch-op spelling ``ssim_value_torch`` in ``tests/helpers.py`` (test infrastructure, not product).
+(``mau_ssim_loss``, csrc/ssim.hip), checked on the GPU against the torch-op spelling ``ssim_value_torch`` in ``tests/_helpers.py`` (test infrastructure, not product).
 That scalar is **parity-unpinned** (no reference fixture can be generated without piq); everything that carries
 gradient is pinned by fixture ``g9_losses.npz``.
 """

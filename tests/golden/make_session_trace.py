@@ -3,7 +3,7 @@
 drivers write into ``session_trace_reports/`` (data only).
 
 The trace of the PARENT of a change that rearranges the host code of the sessions or the drivers is the oracle: check that commit out
-(with this script, ``tests/test_gpu_session_trace.py`` and ``tests/helpers.py`` added: they need nothing but the sessions, the drivers,
+(with this script, ``tests/test_gpu_session_trace.py`` and ``tests/_helpers.py`` added: they need nothing but the sessions, the drivers,
 ``functional.call`` and ``_lib.PROTOTYPES``), build it and run, from the repository root and on a machine WITH the GPU:
 
     python tests/golden/make_session_trace.py

@@ -2,7 +2,6 @@
 (no compute calls without a GPU), the Python binding mirrors the header, and the host-side module
 keeps the reference's constructor / state_dict / error contract."""
 import os
-import re
 
 import numpy as np
 
@@ -10,15 +9,9 @@ import pytest
 import torch
 
 from oracle import unet_ref as R
-from tests.helpers import load_npz, meta_of, sub
+from tests._helpers import header_prototypes, header_symbols, load_npz, meta_of, sub
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-
-
-def header_symbols():
-    txt = open(os.path.join(ROOT, "include", "mau_hip.h")).read()
-    txt = re.sub(r"/\*.*?\*/", "", txt, flags=re.S)
-    return sorted(set(re.findall(r"\b(mau_[a-z0-9_]+)\s*\(", txt)))
 
 
 def test_library_exports_every_header_symbol():
@@ -71,58 +64,28 @@ def test_library_exports_every_header_symbol():
     assert _lib.lib.mau_reduce_tickets_elems() >= 2 * 1024 // 64
 
 
-def header_prototypes():
-    """{name: (return kind, [argument kinds])} of every function declared in include/mau_hip.h; a kind is the ctypes type the binding
-    must use: any pointer and mau_stream_t -> c_void_p (the ``const char*`` RETURN -> c_char_p), scalars -> the matching ctypes type."""
-    import ctypes as C
-    scalars = {"int": C.c_int, "int64_t": C.c_int64, "float": C.c_float, "double": C.c_double, "size_t": C.c_size_t}
-    txt = open(os.path.join(ROOT, "include", "mau_hip.h")).read()
-    txt = re.sub(r"/\*.*?\*/", "", txt, flags=re.S)
-    txt = re.sub(r"//[^\n]*", "", txt)
-    txt = re.sub(r"^\s*#[^\n]*$", "", txt, flags=re.M)                 # (comments are gone: no #define continues on another line)
-
-    def kind(decl, what, is_return=False):
-        words = decl.replace("*", " * ").split()
-        if "*" in words:
-            if is_return:
-                assert words == ["const", "char", "*"], (what, decl)
-                return C.c_char_p
-            return C.c_void_p
-        words = [w for w in words if w != "const"]
-        if not is_return:
-            assert len(words) == 2, f"{what}: cannot read the parameter {decl!r}"       # type + name
-            words = words[:1]
-        assert len(words) == 1, (what, decl)
-        if words[0] == "mau_stream_t":
-            return C.c_void_p
-        assert words[0] in scalars, f"{what}: no ctypes kind for {decl!r}"
-        return scalars[words[0]]
-
-    protos = {}
-    for m in re.finditer(r"([A-Za-z_][\w\s\*]*?)\b(mau_[a-z0-9_]+)\s*\(([^()]*)\)\s*;", txt):
-        ret, name, args = m.group(1), m.group(2), m.group(3).strip()
-        assert name not in protos, name
-        params = [] if args == "void" else [a.strip() for a in args.split(",")]
-        protos[name] = (kind(ret, name, True), [kind(a, name) for a in params])
-    return protos
-
-
 def test_binding_table_matches_header_prototypes():
-    """``_lib.PROTOTYPES`` against the header, by KIND: return type, argument count, and pointer / int / int64 / float / double / size_t
-    per argument, for every entry point.  (ctypes passes surplus arguments of a cdecl call without complaint and an int in a pointer
-    slot lands in the same register: a table row with too few or mistyped entries "works" until a 64-bit value or a float meets it.)"""
+    """``_lib.PROTOTYPES`` against the header, by KIND: the same names, and per name the return type, the argument count, and pointer /
+    int / int64 / float / double / size_t per argument.  (ctypes passes surplus arguments of a cdecl call without complaint and an int
+    in a pointer slot lands in the same register: a table row with too few or mistyped entries "works" until a 64-bit value or a float
+    meets it.)  This is the one place the whole mirror is held to the header: a feature's tests need not repeat it for their symbols."""
     import mau_amd  # noqa: F401
     from mau_amd import _lib
     protos = header_prototypes()
     syms = header_symbols()
     assert sorted(protos) == syms, set(protos) ^ set(syms)              # a prototype the parser cannot read fails here, it is not skipped
-    assert len(protos) == len(_lib.PROTOTYPES) >= 93
-    wrong = {}
+    assert len(protos) >= 93
+    assert set(protos) == set(_lib.PROTOTYPES), {"only in the header": sorted(set(protos) - set(_lib.PROTOTYPES)),
+                                                 "only in the binding": sorted(set(_lib.PROTOTYPES) - set(protos))}
+    wrong = []
     for name, (ret, args) in protos.items():
         bret, bargs = _lib.PROTOTYPES[name]
-        if bret is not ret or len(bargs) != len(args) or any(a is not b for a, b in zip(bargs, args)):
-            wrong[name] = f"header {ret.__name__}({', '.join(a.__name__ for a in args)}) != binding {bret.__name__}({', '.join(a.__name__ for a in bargs)})"
-    assert not wrong, wrong
+        if bret is not ret:
+            wrong.append(f"{name}: returns {ret.__name__} in the header, {bret.__name__} in the binding")
+        if len(bargs) != len(args):
+            wrong.append(f"{name}: {len(args)} arguments in the header, {len(bargs)} in the binding")
+        wrong += [f"{name}: argument {i} is {a.__name__} in the header, {b.__name__} in the binding" for i, (a, b) in enumerate(zip(args, bargs)) if a is not b]
+    assert not wrong, "\n".join(wrong)
     # ... and the loaded functions carry exactly the table's types
     for name, (ret, args) in protos.items():
         fn = getattr(_lib.lib, name)

@@ -9,7 +9,7 @@ import numpy as np
 import pytest
 import torch
 
-from tests.test_capi_and_host import header_prototypes, header_symbols
+from tests._helpers import header_prototypes, header_symbols
 from tests.test_scenario_host import METRICS, load_palette
 
 

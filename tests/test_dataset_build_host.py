@@ -10,11 +10,12 @@ import ctypes
 import json
 import os
 import random
-import re
 import shutil
 
 import numpy as np
 import pytest
+
+from tests._helpers import bits
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 GOLDEN = os.path.join(ROOT, "tests", "golden")
@@ -59,11 +60,6 @@ def recorded_tiles():
             out[(split, name)] = {"input": expand_input(z["cls_a"], z["cls_b"], z["cont"]), "target": z["target"], "metadata": z["metadata"],
                                   "temperature_serie": z["temperature_serie"]}
     return out
-
-
-def bits(x):
-    x = np.ascontiguousarray(x)
-    return x.view({4: np.uint32, 8: np.uint64, 1: np.uint8}[x.dtype.itemsize])
 
 
 def assert_tiles_are_the_recorded_ones(processed_dir, what):
@@ -289,33 +285,10 @@ def test_a_sample_that_cannot_be_read_is_skipped(DB, raw_dir, tmp_path, capsys):
 # --------------------------------------------------------------------------- #
 # the C entry point
 # --------------------------------------------------------------------------- #
-def _header_prototypes():
-    txt = open(os.path.join(ROOT, "include", "mau_hip.h")).read()
-    txt = re.sub(r"/\*.*?\*/", "", txt, flags=re.S)
-    return {name: [a.strip() for a in args.split(",")] if args.strip() not in ("", "void") else []
-            for name, args in re.findall(r"\b(mau_[a-z0-9_]+)\s*\(([^)]*)\)\s*;", txt)}
-
-
-def _kind(decl):
-    if "*" in decl or decl.startswith("mau_stream_t"):
-        return ctypes.c_void_p
-    return {"int": ctypes.c_int, "int64_t": ctypes.c_int64, "size_t": ctypes.c_size_t, "double": ctypes.c_double,
-            "float": ctypes.c_float}[decl.split()[0]]
-
-
-def test_header_and_bindings_agree_on_the_new_symbols(DB):
-    from mau_amd import _lib
-    protos = _header_prototypes()
-    for name, nargs in (("mau_raw_tile_row_elems", 0), ("mau_raw_tile_ws_elems", 2), ("mau_raw_tile_process", 17)):
-        assert len(protos[name]) == nargs and hasattr(ctypes.CDLL(_lib.LIB_PATH), name), name
-        assert [_kind(d) for d in protos[name]] == _lib.PROTOTYPES[name][1], name
-    assert _lib.PROTOTYPES["mau_raw_tile_ws_elems"][0] is ctypes.c_size_t and _lib.PROTOTYPES["mau_raw_tile_process"][0] is ctypes.c_int
-    assert _lib.lib.mau_abi_version() == 5
-    assert _lib.lib.mau_raw_tile_row_elems() == DB.ROW == 16 + 2 + 4 + 4 * 4
-
-
 def test_workspace_arithmetic(DB):
     from mau_amd._lib import lib
+    assert lib.mau_abi_version() == 5
+    assert lib.mau_raw_tile_row_elems() == DB.ROW == 16 + 2 + 4 + 4 * 4
     R, per, ws = lib.mau_raw_tile_row_elems(), lib.mau_reduce_tickets_elems(), lib.mau_raw_tile_ws_elems
     assert ws(3, 62500) == 3 * 16 * R and ws(1, 4096) == R and ws(1, 4097) == 2 * R and ws(per + 5, 62500) == per * 16 * R
     assert ws(0, 64) == 0 and ws(2, 0) == 0 and ws(-1, 64) == 0 and ws(1, (1 << 30) + 1) == 0 and ws(1, 1 << 30) == (1 << 18) * R

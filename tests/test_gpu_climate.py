@@ -18,7 +18,8 @@ import numpy as np
 import pytest
 import torch
 
-from tests.test_climate_host import BASELINE_YEARS, FIX, YEARS, bits, make_grid, recorded_queries
+from tests._helpers import bits, dev, mau  # noqa: F401
+from tests.test_climate_host import BASELINE_YEARS, FIX, YEARS, make_grid, recorded_queries
 
 pytestmark = pytest.mark.gpu
 
@@ -26,16 +27,8 @@ TOL = 1e-10
 
 
 @pytest.fixture(scope="module")
-def CL():
-    import mau_amd
-    assert torch.cuda.is_available(), "GPU tests need a HIP device"
-    from mau_amd import _lib
-    _lib.check(_lib.lib.mau_device_check(), "mau_device_check")
-    return mau_amd.climate
-
-
-def dev(a):
-    return torch.from_numpy(np.ascontiguousarray(a)).cuda()
+def CL(mau):
+    return mau.climate
 
 
 def assert_same_bits(got, want, what):

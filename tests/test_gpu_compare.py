@@ -16,26 +16,15 @@ import numpy as np
 import pytest
 import torch
 
+from tests._helpers import bits, dev, mau, palette, same_bits  # noqa: F401
 from tests.test_compare_host import make_outputs, make_sample
-from tests.test_scenario_host import METRICS, load_palette
+from tests.test_scenario_host import METRICS
 
 pytestmark = pytest.mark.gpu
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SHAPES = [(7, 9), (67, 63), (250, 250)]
 REL = 1e-11
-
-
-@pytest.fixture(scope="module")
-def mau():
-    import mau_amd
-    assert torch.cuda.is_available()
-    return mau_amd
-
-
-@pytest.fixture(scope="module")
-def palette():
-    return load_palette()
 
 
 @pytest.fixture(scope="module")
@@ -47,19 +36,6 @@ def cases():
         out, tgt = make_outputs(np.random.default_rng(200 + i), 3, H, W)
         made[(H, W)] = (out, tgt, C.compare_host(out, tgt, METRICS))
     return made
-
-
-def dev(a):
-    return torch.from_numpy(np.ascontiguousarray(a)).cuda()
-
-
-def bits(a):
-    a = np.ascontiguousarray(a)
-    return a.view({4: np.uint32, 8: np.uint64, 1: np.uint8}[a.dtype.itemsize])
-
-
-def same_bits(a, b):
-    return np.array_equal(bits(a.cpu().numpy()), bits(b.cpu().numpy()))
 
 
 def run_result(C, out, tgt, tickets=None):

@@ -13,8 +13,10 @@ import numpy as np
 import pytest
 import torch
 
-from tests.test_dataset_build_host import (FIX, NORM, assert_kept_is_the_references, assert_tiles_are_the_recorded_ones, bits, make_raw,
-                                           reference_kept, run_build, unpack_raw)
+from tests._helpers import bits, mau  # noqa: F401
+from tests.test_dataset_build_host import raw_dir  # noqa: F401
+from tests.test_dataset_build_host import (FIX, NORM, assert_kept_is_the_references, assert_tiles_are_the_recorded_ones, make_raw,
+                                           reference_kept, run_build)
 
 pytestmark = pytest.mark.gpu
 
@@ -24,12 +26,8 @@ IDS = ["24x24-one-partial-chunk", "64x64-one-full-chunk", "66x66-two-chunks-vec4
 
 
 @pytest.fixture(scope="module")
-def DB():
-    import mau_amd
-    assert torch.cuda.is_available(), "GPU tests need a HIP device"
-    from mau_amd import _lib
-    _lib.check(_lib.lib.mau_device_check(), "mau_device_check")
-    return mau_amd.dataset_build
+def DB(mau):
+    return mau.dataset_build
 
 
 def on_device(DB, raw, norm=None, rows=True, planes=False):
@@ -197,11 +195,6 @@ def test_out_of_range_class_is_counted(DB):
 # --------------------------------------------------------------------------- #
 # the fixture directory, end to end on the device
 # --------------------------------------------------------------------------- #
-@pytest.fixture(scope="module")
-def raw_dir(tmp_path_factory):
-    return unpack_raw(tmp_path_factory.mktemp("buildfix_gpu") / "raw")
-
-
 def test_build_with_the_references_metrics_gives_its_tiles_bit_for_bit(DB, raw_dir, tmp_path, capsys):
     out = tmp_path / "processed"
     res = run_build(DB, raw_dir, out, "cuda", True, batch_size=3)

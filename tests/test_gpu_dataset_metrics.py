@@ -13,6 +13,7 @@ import numpy as np
 import pytest
 import torch
 
+from tests._helpers import mau  # noqa: F401
 from tests.test_dataset_metrics_host import FIX, GOLDEN, assert_rows_match
 
 pytestmark = pytest.mark.gpu
@@ -24,12 +25,8 @@ TOL = 1e-10        # relative to the RMS of the plane: test_gpu_ground_truth.TOL
 
 
 @pytest.fixture(scope="module")
-def D():
-    import mau_amd
-    assert torch.cuda.is_available(), "GPU tests need a HIP device"
-    from mau_amd import _lib
-    _lib.check(_lib.lib.mau_device_check(), "mau_device_check")
-    return mau_amd.dataset_metrics
+def D(mau):
+    return mau.dataset_metrics
 
 
 def make_batch(B, H, W, seed):

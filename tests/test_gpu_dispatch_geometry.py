@@ -10,18 +10,9 @@ import pytest
 import torch
 import torch.nn.functional as TF
 
-from tests.helpers import rel_l2
+from tests._helpers import mau, rel_l2  # noqa: F401
 
 pytestmark = pytest.mark.gpu
-
-
-@pytest.fixture(scope="module")
-def mau():
-    import mau_amd
-    assert torch.cuda.is_available(), "GPU tests need a HIP device"
-    from mau_amd import _lib
-    _lib.check(_lib.lib.mau_device_check(), "mau_device_check")
-    return mau_amd
 
 
 def _to_act(x_nchw, dt):

@@ -15,19 +15,13 @@ import numpy as np
 import pytest
 import torch
 
+from tests._helpers import mau  # noqa: F401
 from tests.test_eval_metrics_host import HEAD, assert_rows_match, eval_truth, write_split
 
 pytestmark = pytest.mark.gpu
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SCALE, SHIFT = [1.0, 7.3], [0.0, 21.5]
-
-
-@pytest.fixture(scope="module")
-def mau():
-    import mau_amd
-    assert torch.cuda.is_available()
-    return mau_amd
 
 
 def coeffs(C):

@@ -17,7 +17,7 @@ import pytest
 import torch
 
 from oracle import unet_ref as R
-from tests.helpers import rel_err, rel_l2
+from tests._helpers import rel_err, rel_l2
 
 pytestmark = pytest.mark.gpu
 LR, WD = 1e-4, 1e-3                     # conf/config.yaml:41,48,52 (bench.py's optimizer)

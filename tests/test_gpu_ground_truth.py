@@ -12,6 +12,8 @@ import numpy as np
 import pytest
 import torch
 
+from tests._helpers import mau  # noqa: F401
+
 pytestmark = pytest.mark.gpu
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -22,12 +24,8 @@ TOL = 1e-10        # relative to the RMS of the plane / bin: n * 2^-53 ~ 7e-12 a
 
 
 @pytest.fixture(scope="module")
-def G():
-    import mau_amd
-    assert torch.cuda.is_available(), "GPU tests need a HIP device"
-    from mau_amd import _lib
-    _lib.check(_lib.lib.mau_device_check(), "mau_device_check")
-    return mau_amd.ground_truth
+def G(mau):
+    return mau.ground_truth
 
 
 # --------------------------------------------------------------------------- #

@@ -13,7 +13,7 @@ import os
 import pytest
 import torch
 
-from tests.helpers import first_difference, patched, recorded_calls
+from tests._helpers import first_difference, mau, patched, recorded_calls  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 
@@ -69,13 +69,6 @@ def record_case(mau, case):
             net(x, ts, md)
         torch.cuda.synchronize()
     return rows
-
-
-@pytest.fixture(scope="module")
-def mau():
-    import mau_amd
-    assert torch.cuda.is_available()
-    return mau_amd
 
 
 @pytest.fixture(scope="module")

@@ -4,18 +4,11 @@ import pytest
 import torch
 
 from oracle import unet_ref as R
-from tests.helpers import load_npz, meta_of, rel_err, rel_l2, sub, t
+from tests._helpers import load_npz, mau, meta_of, rel_err, rel_l2, sub, t  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 
 FULL = ["g5_unet_even.npz", "g5_unet_odd.npz", "g5_unet_noemb.npz", "g6_unetpp.npz", "g6_unetpp_odd.npz"]
-
-
-@pytest.fixture(scope="module")
-def mau():
-    import mau_amd
-    assert torch.cuda.is_available()
-    return mau_amd
 
 
 def build(mau, d, prec):
@@ -128,7 +121,7 @@ def test_full_size_known_answer_fp32(mau):
     (tests/golden/g7_full_summary.json) from the HIP fp32 path."""
     import json
     import os
-    from tests.helpers import GOLDEN
+    from tests._helpers import GOLDEN
     with open(os.path.join(GOLDEN, "g7_full_summary.json")) as f:
         s = json.load(f)
     torch.manual_seed(0)

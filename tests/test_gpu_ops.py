@@ -12,20 +12,11 @@ import torch
 import torch.nn.functional as TF
 
 from oracle import unet_ref as R
-from tests.helpers import load_npz, rel_err, rel_l2, ssim_value_torch, sub, t
+from tests._helpers import load_npz, mau, rel_err, rel_l2, ssim_value_torch, sub, t  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 
 FP32_TOL = 1e-3
-
-
-@pytest.fixture(scope="module")
-def mau():
-    import mau_amd
-    assert torch.cuda.is_available(), "GPU tests need a HIP device"
-    from mau_amd import _lib
-    _lib.check(_lib.lib.mau_device_check(), "mau_device_check")
-    return mau_amd
 
 
 def dev(x):

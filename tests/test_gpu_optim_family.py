@@ -8,18 +8,11 @@ import math
 import pytest
 import torch
 
-from tests.helpers import rel_l2
+from tests._helpers import mau, rel_l2  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 
 FLAGS = dict(temporal_embeddings=False, metadata_embeddings=True)
-
-
-@pytest.fixture(scope="module")
-def mau():
-    import mau_amd
-    assert torch.cuda.is_available()
-    return mau_amd
 
 
 def _net(mau, prec, seed=100):

@@ -8,6 +8,7 @@ import numpy as np
 import pytest
 
 from . import reduce_ref as R
+from ._helpers import same_bits
 
 pytestmark = pytest.mark.gpu
 torch = pytest.importorskip("torch")
@@ -39,14 +40,6 @@ def K():
     return Kit
 
 
-def same_bits(got, want):
-    """equal 64-bit patterns; a NaN matches a NaN (its sign and payload are not values)"""
-    got, want = np.ascontiguousarray(got, dtype=np.float64), np.ascontiguousarray(want, dtype=np.float64)
-    assert got.shape == want.shape
-    ok = (got.view(np.uint64) == want.view(np.uint64)) | (np.isnan(got) & np.isnan(want))
-    assert ok.all(), (np.argwhere(~ok)[:8].tolist(), got[~ok][:8].tolist(), want[~ok][:8].tolist())
-
-
 def _planes(rng, *shape, bad=True):
     x = (rng.standard_normal(shape) * 9.0 + 290.0).astype(np.float32)          # |mean| >> std, as a temperature in kelvin
     if bad and x[0, 0].size > 8:
@@ -66,7 +59,7 @@ def test_plane_moments_bits(K, B, C, HW, off):
     xd = K.off_base(xd) if off else xd
     rows, ws = K.f64(B * C * 4), K.f64(K.lib.mau_plane_moments_ws_elems(B, C, HW))
     K.call("mau_plane_moments", xd.data_ptr(), rows.data_ptr(), ws.data_ptr(), K.tickets.data_ptr(), B, C, HW, None)
-    same_bits(rows.cpu().numpy().reshape(B, C, 4), R.plane_moments(x, vec4=HW % 4 == 0 and not off))
+    assert same_bits(rows.cpu().numpy().reshape(B, C, 4), R.plane_moments(x, vec4=HW % 4 == 0 and not off), nan_matches_nan=True)
 
 
 @pytest.mark.parametrize("B,HW,off", [(2, 1, False), (1, 4096, False), (2, 4097, False), (1, 4100, False), (1, 62500, False), (70, 4097, False),
@@ -81,7 +74,7 @@ def test_tile_stats_bits(K, B, HW, off):
     rows, ws = K.f64(B * R_), K.f64(K.lib.mau_tile_stats_ws_elems(B, HW))
     K.call("mau_tile_stats", ad.data_ptr(), bd.data_ptr(), cd.data_ptr(), td.data_ptr(), rows.data_ptr(), ws.data_ptr(),
            K.tickets.data_ptr(), B, HW, 9, None)
-    same_bits(rows.cpu().numpy().reshape(B, R_), R.tile_stats(a, b, cont, tg, 9, vec4=HW % 4 == 0 and not off))
+    assert same_bits(rows.cpu().numpy().reshape(B, R_), R.tile_stats(a, b, cont, tg, 9, vec4=HW % 4 == 0 and not off), nan_matches_nan=True)
 
 
 @pytest.mark.parametrize("have", [True, False])
@@ -99,7 +92,7 @@ def test_scenario_result_bits(K, N, H, W, have):
     rows, ws = K.f64(N * 5), K.f64(K.lib.mau_scenario_result_ws_elems(N, H, W))
     K.call("mau_scenario_result", od.data_ptr(), tod.data_ptr() if have else None, d1d.data_ptr(), d2d.data_ptr(), 288.5, 9.25,
            nd.data_ptr(), tc.data_ptr(), dl.data_ptr(), rows.data_ptr(), ws.data_ptr(), K.tickets.data_ptr(), N, H, W, None)
-    same_bits(rows.cpu().numpy().reshape(N, 5), R.scenario_result(out, to, d1, d2, 288.5, 9.25))
+    assert same_bits(rows.cpu().numpy().reshape(N, 5), R.scenario_result(out, to, d1, d2, 288.5, 9.25), nan_matches_nan=True)
 
 
 @pytest.mark.parametrize("ncls", [9, 12])
@@ -118,4 +111,4 @@ def test_eval_metrics_bits(K, H, W, ncls):
     rows, ws = K.f64(B * C * R_), K.f64(K.lib.mau_eval_metrics_ws_elems(B, C, H, W, ncls))
     K.call("mau_eval_metrics", od.data_ptr(), td.data_ptr(), cd.data_ptr(), sd.data_ptr(), hd.data_ptr(), rows.data_ptr(), ws.data_ptr(),
            K.tickets.data_ptr(), B, C, H, W, ncls, None)
-    same_bits(rows.cpu().numpy().reshape(B * C, R_), R.eval_metrics(out, tgt, cls, scale, shift, ncls))
+    assert same_bits(rows.cpu().numpy().reshape(B * C, R_), R.eval_metrics(out, tgt, cls, scale, shift, ncls), nan_matches_nan=True)

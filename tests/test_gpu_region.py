@@ -15,37 +15,14 @@ import numpy as np
 import pytest
 import torch
 
-from tests.test_scenario_host import METRICS, load_palette, make_tile
+from tests._helpers import bits, dev, mau, palette, same_bits  # noqa: F401
+from tests.test_scenario_host import METRICS, make_tile
 
 pytestmark = pytest.mark.gpu
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 DTYPES = {"bf16": torch.bfloat16, "fp16": torch.float16, "fp32": torch.float32}
 NCLS = 9
-
-
-@pytest.fixture(scope="module")
-def mau():
-    import mau_amd
-    assert torch.cuda.is_available()
-    return mau_amd
-
-
-@pytest.fixture(scope="module")
-def palette():
-    return load_palette()
-
-
-def dev(a):
-    return torch.from_numpy(np.ascontiguousarray(a)).cuda()
-
-
-def bits(t):
-    return t.contiguous().view(torch.int32 if t.element_size() == 4 else torch.int16)
-
-
-def same_bits(a, b):
-    return a.shape == b.shape and torch.equal(bits(a), bits(b))
 
 
 def make_region(rng, Hr, Wr, edited=1 / 3):

@@ -13,7 +13,8 @@ import numpy as np
 import pytest
 import torch
 
-from tests.test_scenario_host import METRICS, load_palette, make_canvas, make_tile
+from tests._helpers import bits, dev, mau, palette, same_bits  # noqa: F401
+from tests.test_scenario_host import METRICS, make_canvas, make_tile
 
 pytestmark = pytest.mark.gpu
 
@@ -23,31 +24,11 @@ DTYPES = {"bf16": torch.bfloat16, "fp16": torch.float16, "fp32": torch.float32}
 
 
 @pytest.fixture(scope="module")
-def mau():
-    import mau_amd
-    assert torch.cuda.is_available()
-    return mau_amd
-
-
-@pytest.fixture(scope="module")
-def palette():
-    return load_palette()
-
-
-@pytest.fixture(scope="module")
 def tile():
     """One base tile (host arrays) and its normalised planes, shared and never written."""
     from mau_amd import scenario as S
     dw, rgb, ndvi, temp = make_tile(np.random.default_rng(10), H, W)
     return dw, rgb, ndvi, temp, S.normalized_planes_host(rgb, ndvi, temp, METRICS)
-
-
-def dev(a):
-    return torch.from_numpy(np.ascontiguousarray(a)).cuda()
-
-
-def bits(t):
-    return t.contiguous().view(torch.int32 if t.element_size() == 4 else torch.int16)
 
 
 def device_pack(S, tile, canvases, palette, dtype):
@@ -187,10 +168,6 @@ def test_result_more_scenarios_than_tickets(mau):
 # the session
 # --------------------------------------------------------------------------- #
 TH, TW, CH, CW = 48, 48, 64, 80
-
-
-def same_bits(a, b):
-    return torch.equal(bits(a), bits(b))
 
 
 @pytest.mark.parametrize("model_type", ["unet", "unet++"])

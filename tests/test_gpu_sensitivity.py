@@ -11,18 +11,11 @@ import pytest
 import torch
 
 from oracle import unet_ref as R
-from tests.helpers import rel_err, rel_l2
+from tests._helpers import mau, rel_err, rel_l2  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-
-
-@pytest.fixture(scope="module")
-def mau():
-    import mau_amd
-    assert torch.cuda.is_available()
-    return mau_amd
 
 
 def small_net(mau, model_type, prec, seed=5, base_filters=8, **kw):

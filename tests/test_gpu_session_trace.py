@@ -1,7 +1,7 @@
 """The launch sequence of the captured sessions and of the two test-split drivers: every call through ``functional.call`` while a
 session is built and used, or a driver walks a small split, compared call for call with ``tests/golden/session_trace.json`` -- recorded
 by ``tests/golden/make_session_trace.py`` at the PARENT of a change that moves their host code around without changing what is
-launched.  A call is encoded as in ``tests/test_gpu_launch_trace.py`` (``tests/helpers.py``: scalars verbatim, pointers null or not,
+launched.  A call is encoded as in ``tests/test_gpu_launch_trace.py`` (``tests/_helpers.py``: scalars verbatim, pointers null or not,
 the stream "main" or "side").  The warm-up runs on a side stream and a capture on the capture's own: both read "side"; a replay
 launches through no ``call`` and leaves no row, the copies and launches around it do.
 
@@ -20,7 +20,7 @@ import numpy as np
 import pytest
 import torch
 
-from tests.helpers import first_difference, recorded_calls
+from tests._helpers import dev, first_difference, mau, recorded_calls  # noqa: F401
 from tests.test_eval_metrics_host import write_split
 from tests.test_scenario_host import METRICS, load_palette, make_canvas, make_tile
 
@@ -41,10 +41,6 @@ TEST_TILES = [("Alpha Town", 1, (2019, 1), (2021, 2), None, 12), ("Beta", 2, (20
 EVAL_METRICS = {"meta_mean": [20.0, 10.0, 3.0, 1.0], "meta_std": [15.0, 60.0, 2.0, 0.5], "temp_mean": 14.5, "temp_std": 8.25}
 REPORTS = ("st_unet_metaemb_3_jobe_evaluation.csv", "st_unet_metaemb_3_jobe_info.csv", "st_unet_metaemb_3_jobc_evaluation.csv",
            "st_unet_metaemb_3_jobc_info.csv", "st_unet++_emb_4_jobc_evaluation.csv", "st_unet++_emb_4_jobc_info.csv", "st_paired_tests.csv")
-
-
-def dev(a):
-    return torch.from_numpy(np.ascontiguousarray(a)).cuda()
 
 
 def recording(mau):
@@ -147,13 +143,6 @@ def eval_drivers(mau, work):
 
 CASES = {"graphed_inference": graphed_inference, "scenario_session": scenario_session, "comparison_session": comparison_session,
          "region_session": region_session, "eval_drivers": eval_drivers}
-
-
-@pytest.fixture(scope="module")
-def mau():
-    import mau_amd
-    assert torch.cuda.is_available()
-    return mau_amd
 
 
 @pytest.fixture(scope="module")

@@ -14,6 +14,7 @@ import torch
 import torch.nn.functional as TF
 
 from tests import spatial_ref as SR
+from tests._helpers import _bits_equal, _call, _nbits_differ, _stream, mau  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 
@@ -24,27 +25,9 @@ DT_IDS = ["fp32", "bf16", "fp16"]
 pad8 = SR.pad8
 
 
-@pytest.fixture(scope="module")
-def mau():
-    import mau_amd
-    assert torch.cuda.is_available(), "GPU tests need a HIP device"
-    from mau_amd import _lib
-    _lib.check(_lib.lib.mau_device_check(), "mau_device_check")
-    return mau_amd
-
-
 def _code(dt):
     from mau_amd import _lib
     return {torch.float32: _lib.MAU_F32, torch.bfloat16: _lib.MAU_BF16, torch.float16: _lib.MAU_F16}[dt]
-
-
-def _stream():
-    return torch.cuda.current_stream().cuda_stream
-
-
-def _call(name, *args):
-    from mau_amd._lib import call
-    call(name, *args)
 
 
 def _plan(N, h, w, H, W, C):
@@ -97,16 +80,6 @@ class Buf:
         assert bool(torch.isnan(b[..., :choff]).all()) and bool(torch.isnan(b[..., choff + C8:]).all()), "channels outside [choff, choff + C8) were written"
         assert bool((b[..., choff + C:choff + C8] == 0).all()), "pad lanes are not 0"
         return b[..., choff:choff + C].permute(0, 3, 1, 2).contiguous()
-
-
-def _bits_equal(a, b):
-    a, b = torch.as_tensor(a).float().contiguous(), torch.as_tensor(b).float().contiguous()
-    return a.shape == b.shape and bool((a.view(torch.int32) == b.view(torch.int32)).all())
-
-
-def _nbits_differ(a, b):
-    a, b = torch.as_tensor(a).float().contiguous(), torch.as_tensor(b).float().contiguous()
-    return int((a.view(torch.int32) != b.view(torch.int32)).sum())
 
 
 def _randn(shape, seed, dt):

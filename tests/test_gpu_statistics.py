@@ -12,6 +12,7 @@ import numpy as np
 import pytest
 import torch
 
+from tests._helpers import mau, same_bits  # noqa: F401
 from tests.test_eval_metrics_host import write_split
 from tests.test_statistics_host import HEAD, random_rows
 
@@ -24,13 +25,6 @@ SCALE, SHIFT = [1.0, 7.3], [0.0, 21.5]
 SHAPES = [(3, 5), (62, 62), (70, 70), (33, 129), (2, 4100)]
 
 
-@pytest.fixture(scope="module")
-def mau():
-    import mau_amd
-    assert torch.cuda.is_available()
-    return mau_amd
-
-
 def make_case(M, B, C, H, W, ncls, seed):
     rng = np.random.default_rng(seed)
     out = rng.standard_normal((M, B, C, H, W)).astype(np.float32)
@@ -40,15 +34,6 @@ def make_case(M, B, C, H, W, ncls, seed):
     out[M - 1, 1, 0, H // 2, W // 3] = np.nan                    # one model's output holds a NaN and an inf
     out[M - 1, 2, 1, 0, W - 1] = np.inf
     return torch.from_numpy(out).cuda(), torch.from_numpy(tgt).cuda(), torch.from_numpy(cls).cuda()
-
-
-def same_bits(a, b):
-    ia, ib = a.contiguous().view(torch.int64), b.contiguous().view(torch.int64)
-    if not torch.equal(ia, ib):
-        at = (ia != ib).nonzero()[:8].tolist()
-        print("bits differ at", [(tuple(i), hex(ia[tuple(i)].item() & (2 ** 64 - 1)), hex(ib[tuple(i)].item() & (2 ** 64 - 1))) for i in at])
-        return False
-    return True
 
 
 # ---- 1. the multi kernel against the one-model kernel ------------------------------------------------------------

@@ -33,6 +33,7 @@ import pytest
 import torch
 
 from tests import temporal_ref as TR
+from tests._helpers import _bits_equal, _call, _nbits_differ, _stream, mau  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 
@@ -40,23 +41,6 @@ NAN = float("nan")
 PAD = 64                                                      # sentinel floats in front of and behind every buffer
 FLOOR = 2.0 ** -20
 FACTOR = 16.0
-
-@pytest.fixture(scope="module")
-def mau():
-    import mau_amd
-    assert torch.cuda.is_available(), "GPU tests need a HIP device"
-    from mau_amd import _lib
-    _lib.check(_lib.lib.mau_device_check(), "mau_device_check")
-    return mau_amd
-
-
-def _stream():
-    return torch.cuda.current_stream().cuda_stream
-
-
-def _call(name, *args):
-    from mau_amd._lib import call
-    call(name, *args)
 
 
 class In:
@@ -95,18 +79,6 @@ class Out:
         body = r[PAD:PAD + self.n]
         assert bool(torch.isfinite(body).all()), f"{int((~torch.isfinite(body)).sum())} of {self.n} elements not finite (unwritten, or poisoned by a read outside an input)"
         return body.view(self.shape).clone()
-
-
-def _bits(a):
-    return a.detach().float().contiguous().view(torch.int32)
-
-
-def _bits_equal(a, b):
-    return a.shape == b.shape and bool((_bits(a) == _bits(b)).all())
-
-
-def _nbits_differ(a, b):
-    return int((_bits(a) != _bits(b)).sum())
 
 
 # ---- the tolerance rule -----------------------------------------------------------------------------------------------------------------

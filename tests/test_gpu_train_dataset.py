@@ -6,21 +6,14 @@ import numpy as np
 import pytest
 import torch
 
+from tests._helpers import mau  # noqa: F401
+
 pytestmark = pytest.mark.gpu
 
 H, W, N_TS = 48, 40, 24
 CKPT_KEYS = {"epoch", "step", "model_state_dict", "optimizer_state_dict", "loss", "hyperparameters", "model_type", "study_name", "trial_id",
              "metadata_input_length"}
 TERM_KEYS = {"total", "mse", "gradient", "pixel", "ssim"}
-
-
-@pytest.fixture(scope="module")
-def mau():
-    import mau_amd
-    assert torch.cuda.is_available(), "GPU tests need a HIP device"
-    from mau_amd import _lib
-    _lib.check(_lib.lib.mau_device_check(), "mau_device_check")
-    return mau_amd
 
 
 def write_tiles(folder, n, rng):

@@ -11,7 +11,7 @@ import pytest
 import torch
 
 from oracle import unet_ref as R
-from tests.helpers import GOLDEN, load_npz, meta_of, rel_err, sub, t
+from tests._helpers import GOLDEN, load_npz, meta_of, rel_err, sub, t
 
 torch.set_num_threads(max(1, min(8, os.cpu_count() or 1)))
 

@@ -6,7 +6,7 @@ import ctypes
 import numpy as np
 import pytest
 
-from tests.test_capi_and_host import header_prototypes, header_symbols
+from tests._helpers import header_prototypes, header_symbols
 from tests.test_scenario_host import METRICS, load_palette, make_tile
 
 # (Hr, Wr, T, overlap): ragged both ways; no overlap with a moved-back last window; an exact multiple; one window; small odd sizes

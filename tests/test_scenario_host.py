@@ -8,7 +8,7 @@ import os
 import numpy as np
 import pytest
 
-from tests.test_capi_and_host import header_prototypes, header_symbols
+from tests._helpers import header_prototypes, header_symbols
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 

@@ -10,7 +10,7 @@ import torch
 import torch.nn.functional as TF
 
 from tests import spatial_ref as SR
-from tests.helpers import load_npz
+from tests._helpers import load_npz
 
 
 @pytest.fixture(scope="module")

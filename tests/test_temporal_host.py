@@ -5,7 +5,7 @@ import pytest
 import torch
 
 from tests import temporal_ref as TR
-from tests.helpers import load_npz, rel_err, sub, t
+from tests._helpers import load_npz, rel_err, sub, t
 
 F64 = torch.float64
 LSTM_CASES = [(2, 1, 1), (3, 9, 5), (2, 17, 33), (1, 41, 128)]
