@@ -672,7 +672,8 @@ int mau_bn_relu_bwd_reduce(const void* da, int ldda, const void* y, int ldy, con
                            const float* mean, const float* invstd, float* slab, int ldslab, int dtype, int64_t npix,
                            int C, mau_stream_t stream) {
   MAU_REQUIRE(da && y && scale && shift && mean && invstd && slab && npix > 0 && C > 0, "bn_relu_bwd_reduce: bad arguments");
-  MAU_REQUIRE(ldda % 8 == 0 && ldy % 8 == 0 && ldslab >= C, "bn_relu_bwd_reduce: bad ld");
+  const int C8 = round_up(C, 8);                             // (the kernel loads whole 8-channel vectors of da and y)
+  MAU_REQUIRE(ldda % 8 == 0 && ldy % 8 == 0 && ldda >= C8 && ldy >= C8 && ldslab >= C, "bn_relu_bwd_reduce: bad ld");
   dim3 grid(mau_bn_bwd_rows(npix), ceil_div(C, 64));
   MAU_DISPATCH_DTYPE(dtype, MAU_LAUNCH(bn_relu_bwd_reduce_kernel<T>, grid, dim3(256), 0, (hipStream_t)stream,
                                                (const T*)da, ldda, (const T*)y, ldy, scale, shift, mean, invstd, slab,
@@ -683,9 +684,9 @@ int mau_bn_relu_bwd_reduce(const void* da, int ldda, const void* y, int ldy, con
 int mau_bn_relu_bwd_apply(const void* da, int ldda, const void* y, int ldy, const float* scale, const float* shift,
                           const float* mean, const float* invstd, const double* sums, double count, void* dy, int lddy,
                           int dtype, int64_t npix, int C, mau_stream_t stream) {
-  MAU_REQUIRE(da && y && dy && sums && npix > 0 && C > 0 && count >= 0, "bn_relu_bwd_apply: bad arguments");
+  MAU_REQUIRE(da && y && dy && sums && scale && shift && mean && invstd && npix > 0 && C > 0 && count >= 0, "bn_relu_bwd_apply: bad arguments");
   const int C8 = round_up(C, 8);
-  MAU_REQUIRE(ldda % 8 == 0 && ldy % 8 == 0 && lddy % 8 == 0 && lddy >= C8, "bn_relu_bwd_apply: bad ld");
+  MAU_REQUIRE(ldda % 8 == 0 && ldy % 8 == 0 && lddy % 8 == 0 && ldda >= C8 && ldy >= C8 && lddy >= C8, "bn_relu_bwd_apply: bad ld");
   // up to 64 pixels per thread and as few as 256 workgroups: this kernel's per-channel set-up (6 coefficient vectors,
   // fp64 means) is what the mid-size layers were paying for (C=256: 61 -> 36 us, scripts/elementwise_bench.py)
   const int pixb = pixvec_pixels_per_block(C8 / 8, npix, 64, 256);

@@ -1033,3 +1033,36 @@ def test_bn_stats_finalize_every_length_matches_two_launch_form(mau):
         eps = float(torch.tensor(1e-5, dtype=torch.float32))       # the kernel receives eps as a float
         assert torch.allclose(mean, m.float(), rtol=3e-7, atol=1e-30) and torch.allclose(invstd, (1.0 / torch.sqrt(var + eps)).float(), rtol=3e-7, atol=0), rows
         assert torch.allclose(scale, gamma * invstd, rtol=1e-6, atol=0) and torch.allclose(shift, beta - mean * scale, rtol=1e-5, atol=1e-6), rows
+        # the running statistics against their definition (momentum 0.1 from running_mean = 0, running_var = 1; unbiased variance,
+        # the biased one itself when there is one element)
+        unbiased = var * count / (count - 1) if count > 1 else var
+        assert torch.allclose(rm.double(), 0.9 * 0.0 + 0.1 * m.cuda(), rtol=1e-6, atol=1e-30), rows
+        assert torch.allclose(rv.double(), 0.9 * 1.0 + 0.1 * unbiased.cuda(), rtol=1e-6, atol=0), rows
+
+
+@pytest.mark.parametrize("C", [1, 70, 300])
+def test_bn_coeffs_eval_matches_its_definition(mau, C):
+    """mau_bn_coeffs_eval against fp64: invstd = 1 / sqrt(running_var + eps), scale = gamma * invstd, shift = beta - running_mean * scale;
+    with the optional mean / invstd outputs and without them; nothing written behind C elements"""
+    from mau_amd._lib import call
+    st = torch.cuda.current_stream().cuda_stream
+    g = torch.Generator().manual_seed(C)
+    gamma, beta, rmean = (torch.randn(C, generator=g).cuda() for _ in range(3))
+    rvar = (torch.rand(C, generator=g) * 4 + 0.01).cuda()
+    eps = float(torch.tensor(1e-5, dtype=torch.float32))           # the kernel receives eps as a float
+    invstd = 1.0 / torch.sqrt(rvar.double() + eps)
+    scale = gamma.double() * invstd
+    shift = beta.double() - rmean.double() * scale
+    for with_moments in (False, True):
+        outs = [torch.full((C + 8,), float("nan"), device="cuda") for _ in range(4)]
+        call("mau_bn_coeffs_eval", gamma.data_ptr(), beta.data_ptr(), rmean.data_ptr(), rvar.data_ptr(), 1e-5, outs[0].data_ptr(), outs[1].data_ptr(),
+             outs[2].data_ptr() if with_moments else None, outs[3].data_ptr() if with_moments else None, C, st)
+        torch.cuda.synchronize()
+        assert all(bool(torch.isnan(o[C:]).all()) for o in outs)
+        assert torch.allclose(outs[0][:C].double(), scale, rtol=1e-6, atol=0)
+        # (shift is a difference: its error is relative to the larger of its two terms)
+        assert bool(((outs[1][:C].double() - shift).abs() <= 1e-6 * torch.maximum(beta.double().abs(), (rmean.double() * scale).abs())).all())
+        if with_moments:
+            assert torch.equal(outs[2][:C], rmean) and torch.allclose(outs[3][:C].double(), invstd, rtol=1e-6, atol=0)
+        else:
+            assert bool(torch.isnan(outs[2]).all()) and bool(torch.isnan(outs[3]).all())

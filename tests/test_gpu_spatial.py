@@ -14,12 +14,10 @@ import torch
 import torch.nn.functional as TF
 
 from tests import spatial_ref as SR
-from tests._helpers import _bits_equal, _call, _nbits_differ, _stream, mau  # noqa: F401
+from tests._helpers import NAN, SLACK, Buf, _bits_equal, _call, _nbits_differ, _stream, mau  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 
-NAN = float("nan")
-SLACK = 3                                                     # pixels of sentinel in front of and behind every tensor
 DTYPES = [torch.float32, torch.bfloat16, torch.float16]
 DT_IDS = ["fp32", "bf16", "fp16"]
 pad8 = SR.pad8
@@ -33,53 +31,6 @@ def _code(dt):
 def _plan(N, h, w, H, W, C):
     from mau_amd import _lib
     return _lib.resize_bilinear_plan(N, h, w, H, W, C)
-
-
-class Buf:
-    """(npix, ld) tensor of ``dt`` with SLACK sentinel pixels at both ends, staged on the CPU, NaN everywhere until written"""
-
-    def __init__(self, npix, ld, dt, fill=NAN):
-        self.npix, self.ld, self.dt = npix, ld, dt
-        self.host = torch.full((npix + 2 * SLACK, ld), fill, dtype=dt)
-        self.dev = None
-
-    @property
-    def body(self):
-        return self.host[SLACK:SLACK + self.npix]
-
-    def put(self, x_nchw, choff=0):
-        """channels [choff, choff + C) <- x (N, C, H, W), pad lanes up to the next multiple of 8 <- 0"""
-        N, C, H, W = x_nchw.shape
-        v = self.body.view(N, H, W, self.ld)
-        v[..., choff:choff + C] = x_nchw.permute(0, 2, 3, 1).to(self.dt)
-        v[..., choff + C:choff + pad8(C)] = 0
-        return self
-
-    def cuda(self):
-        self.dev = self.host.cuda()
-        return self
-
-    @property
-    def ptr(self):
-        if self.dev is None:
-            self.cuda()
-        return self.dev.data_ptr() + SLACK * self.ld * self.dev.element_size()
-
-    def back(self):
-        """the tensor's pixels after the call; the sentinel pixels must be untouched"""
-        torch.cuda.synchronize()
-        r = self.dev.cpu()
-        assert bool(torch.isnan(r[:SLACK].float()).all()) and bool(torch.isnan(r[SLACK + self.npix:].float()).all()), "pixels outside the tensor were written"
-        return r[SLACK:SLACK + self.npix]
-
-    def get(self, shape, choff=0):
-        """(N, C, H, W) float32 of channels [choff, choff + C); every channel outside [choff, choff + C8) still NaN, pad lanes 0"""
-        N, C, H, W = shape
-        b = self.back().view(N, H, W, self.ld).float()
-        C8 = pad8(C)
-        assert bool(torch.isnan(b[..., :choff]).all()) and bool(torch.isnan(b[..., choff + C8:]).all()), "channels outside [choff, choff + C8) were written"
-        assert bool((b[..., choff + C:choff + C8] == 0).all()), "pad lanes are not 0"
-        return b[..., choff:choff + C].permute(0, 3, 1, 2).contiguous()
 
 
 def _randn(shape, seed, dt):
