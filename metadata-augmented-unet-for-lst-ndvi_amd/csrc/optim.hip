@@ -66,7 +66,8 @@ __global__ __launch_bounds__(1024) void opt_pack_kernel(const AdamWPackDesc* __r
       if (RULE == MAU_OPT_SGD) {
         // torch's order and roundings (measured bit for bit against torch.optim.SGD on gfx950): grad.add(p, alpha=wd) and
         // p.add_(g, alpha=-lr) are one fused multiply-add each, buf.mul_(mu).add_(g) is two operations -- the product is rounded
-        // (opaque() keeps the compiler from contracting it)
+        // (opaque() keeps the compiler from contracting it).  The rule itself -- order, buffer, nesterov term, grad_scale in front
+        // of the decay -- is pinned bit for bit on inputs where no rounding occurs by tests/test_gpu_optim_pack.py::test_sgd_exact
         if (wd != 0.f) g = fmaf(wd, p, g);
         if (d.m != nullptr) {
           const float buf = opaque(beta1 * d.m[idx]) + g;
