@@ -21,7 +21,8 @@
  * inputs/outputs are always fp32 in the reference's own layouts (NCHW, OIHW).
  *
  * Each entry point names the reference code it replaces (file:line in the
- * reference repo).
+ * reference repo).  The rank tests of checkpoints (mau_rank_tests) return exact
+ * int64 rank sums, obtained by counting: see "statistical comparison" below.
  */
 #ifndef MAU_HIP_H
 #define MAU_HIP_H
@@ -510,6 +511,33 @@ int mau_paired_entry_elems(int M);
 size_t mau_paired_table_elems(int M, int C, int ncls);
 int mau_paired_accumulate(const double* rows, const unsigned char* group, double* table, int M, int B, int C, int ncls,
                           mau_stream_t stream);
+/* mau_rank_tests: the rank tests of the same page (section 7 pairwise Wilcoxon, section 3 Mann-Whitney known against unknown cities,
+ * sections 1-2 the pooled minimum and 98th percentile) as EXACT INTEGERS, ranks by counting: for element i of a multiset v,
+ * less_i = #{j : v_j < v_i}, eq_i = #{j : v_j == v_i} (i included), twice the mid-rank = 2 less_i + eq_i + 1, the tie term
+ * sum over tie groups (t^3 - t) = sum_i (eq_i^2 - 1).  Additive to ABI 5.
+ *   cols: (Q, M, Ncap) fp64 column store, the first N entries of a column are read and nothing behind them; M in [1,8];
+ *   Q in [1,4096]; 1 <= N <= mau_rank_max_samples() = 2^20 (sum eq^2 stays inside int64); Ncap >= N;  known: (N) uint8, non-zero =
+ *   a known city.  For a q, a sample with a non-finite value in ANY model is dropped for all of them (`skipped`).
+ *   table: mau_rank_table_elems(M, Q) = Q * (7 M (M - 1) / 2 + 4 M + 4) int64, written whole by the call; per q, in this order:
+ *     per pair i < j (row-major: (0,1), (0,2), ..., (M-2,M-1)), d = x_i - x_j in fp64, |d| ranked over the kept samples with d != 0:
+ *       [0] n_used  [1] n_zero (kept, d == 0)  [2] skipped  [3] 2 W+ (d > 0)  [4] 2 W- (d < 0)  [5] tie term
+ *       [6] with at most 13 kept samples sum_i 16^less_i, else 0: bits [4 p, 4 p + 4) hold the size of the tie group that starts at
+ *           rank position p (what the exact null distribution of a small sample WITH ties needs beyond the sums)
+ *     per model, its kept values ranked, known and unknown cities pooled:
+ *       [0] n_known  [1] n_unknown  [2] 2 R_known (twice the rank sum of the known cities)  [3] tie term
+ *     the kept values of all M models pooled, n = M * kept samples:
+ *       [0] n  [1] the minimum  [2], [3] the order statistics lo = floor(0.98 (n - 1)) = (n - 1) * 49 / 50 and min(lo + 1, n - 1),
+ *       as fp64 bit patterns of x + 0.0 (0 when n = 0); element i is the k-th order statistic iff less_i <= k < less_i + eq_i.
+ *   ws: mau_rank_ws_elems(Q, N) int64 of workspace (the kept counts and flags).
+ * One thread per i, mau_rank_tile() = 256 values of j staged in LDS per step, int64 partial sums joined by integer atomic adds: the
+ * bits do not depend on any order.  Four launches on the stream, no host synchronisation.  The size queries return 0 for
+ * arguments the call refuses. */
+int mau_rank_tile(void);
+int mau_rank_max_samples(void);
+size_t mau_rank_table_elems(int M, int Q);
+size_t mau_rank_ws_elems(int Q, int N);
+int mau_rank_tests(const double* cols, const unsigned char* known, int64_t* table, int64_t* ws, int M, int Q, int N, int Ncap,
+                   mau_stream_t stream);
 
 /* ---- scenario sessions: a painted canvas -> the network's input, the head's output -> temperature change (the app's per-click path,
  *      app/Home.py:333-411 with app/processing_utils.py:70-181), ONE launch each.  Additive to ABI 5 ----

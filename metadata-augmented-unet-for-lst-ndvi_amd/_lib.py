@@ -125,6 +125,11 @@ PROTOTYPES = {
     "mau_paired_entry_elems": (_i, [_i]),
     "mau_paired_table_elems": (_sz, [_i, _i, _i]),
     "mau_paired_accumulate": (_i, [_p, _p, _p, _i, _i, _i, _i, _p]),
+    "mau_rank_tile": (_i, []),
+    "mau_rank_max_samples": (_i, []),
+    "mau_rank_table_elems": (_sz, [_i, _i]),
+    "mau_rank_ws_elems": (_sz, [_i, _i]),
+    "mau_rank_tests": (_i, [_p, _p, _p, _p, _i, _i, _i, _i, _p]),
     "mau_scenario_max_classes": (_i, []),
     "mau_scenario_pack": (_i, [_p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _i, _p, _i, _i, _i, _i, _i, _i, _i, _p]),
     "mau_scenario_result_row_elems": (_i, []),

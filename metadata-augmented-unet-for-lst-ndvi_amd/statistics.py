@@ -18,7 +18,7 @@ does.  One table serves the paired t-test of models i, j (mean difference mean_i
 extended to co-moments).
 
     python -m mau_amd.statistics a.pth b.pth [c.pth ...] --processed-dir data/processed --device gpu [--study-name test]
-           [--jobid J] [--batch-size N] [--precision P] [--metrics-json F] [--output-dir reports/tests]
+           [--jobid J] [--batch-size N] [--precision P] [--metrics-json F] [--output-dir reports/tests] [--rank-tests]
 
 writes each model's ``*_evaluation.csv`` / ``*_info.csv``, ``<study>_paired_tests.csv`` and prints the reference's table; with one
 checkpoint it prints the single-model interpretation (thresholds and layout of ``interpret_metrics``, the verdicts in this
@@ -29,9 +29,13 @@ of ANY of the M models drops the sample from that entry for ALL models, and the 
 the two agree.
 
 ``paired_accumulate_host`` is the float64 twin of the kernel, operation for operation.  The Student-t survival function is the
-regularised incomplete beta function by Lentz's continued fraction in plain Python: no scipy, no pandas at run time.  Wilcoxon,
-Mann-Whitney, plots and the page's binned trend correlations are out of scope: they need ranks or figures and read the per-sample
-CSVs this tool writes.
+regularised incomplete beta function by Lentz's continued fraction in plain Python: no scipy, no pandas at run time.
+
+``--rank-tests`` adds the page's rank tests from the same pass (``rank_tests.RankStats``: the overall mae / rmse columns stay on the
+device, ``mau_rank_tests`` ranks them by counting, one more read-back): the pairwise Wilcoxon p-values, Mann-Whitney U of known
+against unknown cities and the pooled 98th percentile, written to ``<study>_rank_tests.csv`` and printed as the page's two tables.
+Without the flag nothing changes.  Plots and the page's binned trend correlations are out of scope: they need figures and read
+the per-sample CSVs this tool writes.
 """
 from __future__ import annotations
 
@@ -453,11 +457,12 @@ class PairedStats:
 @torch.no_grad()
 def compare_checkpoints(checkpoint_paths: Sequence[str], processed_dir: str, *, batch_size: Optional[int] = None,
                         precision: Optional[str] = None, study_name: str = "test", jobid: str = "", output_dir: str = "reports/tests",
-                        metrics_json: Optional[str] = None, device: str = "cuda") -> dict:
+                        metrics_json: Optional[str] = None, device: str = "cuda", rank_tests: bool = False) -> dict:
     """One pass over the ``test`` split of ``processed_dir`` for M checkpoints.  Writes every model's reports (as
     ``evaluate.evaluate_checkpoint`` does, same rows) and ``<study>_paired_tests.csv``.  Returns {'names', 'channels', 'table',
     'tests', 'rows' (per model), 'report_paths', 'info_paths', 'tests_path'}.  batch_size: default the first checkpoint's
-    ``hyperparameters.batch_size``, else 16."""
+    ``hyperparameters.batch_size``, else 16.  rank_tests: also the rank tests of ``rank_tests.py`` -- 'rank_table', 'rank_tests',
+    'axis_ranges', 'rank_tests_path' (``<study>_rank_tests.csv``)."""
     from .checkpoint import resolve_embedding_flags
     M = len(checkpoint_paths)
     if not 1 <= M <= MAX_MODELS:
@@ -472,7 +477,7 @@ def compare_checkpoints(checkpoint_paths: Sequence[str], processed_dir: str, *, 
     if len(set(names)) != M:
         raise ValueError(f"compare_checkpoints: the checkpoints' reports would overwrite each other ({names}): give them distinct trial ids")
     rows: List[List[dict]] = [[] for _ in range(M)]
-    stats, buf, ws = None, None, None
+    stats, buf, ws, ranks = None, None, None, None
     for _host, batch, sample_idx, infos in walk_test_split(loader, known, device):
         packed: Dict[torch.dtype, tuple] = {}                       # the batch is packed once per network dtype
         gids = [group_id(info["is_known_city"], info["t1_year"]) for info in infos]
@@ -490,6 +495,11 @@ def compare_checkpoints(checkpoint_paths: Sequence[str], processed_dir: str, *, 
         if stats is None:
             stats = PairedStats(M, Co, batch.num_classes, buf.device)
         stats.update(mrows, torch.tensor(gids, dtype=torch.uint8).to(buf.device, non_blocking=True))
+        if rank_tests:
+            if ranks is None:
+                from .rank_tests import RankStats
+                ranks = RankStats(M, Co, len(loader.dataset), buf.device)
+            ranks.update(mrows, torch.tensor([int(bool(info["is_known_city"])) for info in infos], dtype=torch.uint8).to(buf.device, non_blocking=True))
         host_rows = mrows.cpu()                                     # the one copy of the batch
         for m in range(M):
             rows[m] += metric_rows(EvalMetrics(host_rows[m], batch.num_classes), sample_idx, channels, infos)
@@ -499,9 +509,16 @@ def compare_checkpoints(checkpoint_paths: Sequence[str], processed_dir: str, *, 
     written = [write_reports(rows[m], output_dir, study_name, *idents[m], jobid) for m in range(M)]
     tests = paired_tests(table, names, channels, DW_CLASS_NAMES[:stats.num_classes] if stats.num_classes <= len(DW_CLASS_NAMES)
                          else [f"class_{k}" for k in range(stats.num_classes)])
-    return {"names": names, "channels": channels, "table": table, "tests": tests, "rows": rows,
-            "report_paths": [w[0] for w in written], "info_paths": [w[1] for w in written],
-            "tests_path": write_paired_tests(tests, output_dir, study_name)}
+    res = {"names": names, "channels": channels, "table": table, "tests": tests, "rows": rows,
+           "report_paths": [w[0] for w in written], "info_paths": [w[1] for w in written],
+           "tests_path": write_paired_tests(tests, output_dir, study_name)}
+    if rank_tests:
+        from . import rank_tests as R_
+        rank_table = ranks.result()                                 # the one read-back of the rank tests
+        rank_rows = R_.rank_test_rows(rank_table, names, channels, table, ranks.n)
+        res.update(rank_table=rank_table, rank_tests=rank_rows, axis_ranges=R_.axis_ranges(rank_table, channels, M),
+                   rank_tests_path=R_.write_rank_tests(rank_rows, output_dir, study_name))
+    return res
 
 
 # --------------------------------------------------------------------------- #
@@ -518,24 +535,34 @@ def main(argv=None) -> int:
     p.add_argument("--precision", default=None, choices=["bf16", "fp16", "fp32"])
     p.add_argument("--metrics-json", default=None, help="normalization_metrics.json (default: the one in --processed-dir, if any)")
     p.add_argument("--output-dir", default="reports/tests")
+    p.add_argument("--rank-tests", action="store_true", help="also the pairwise Wilcoxon and the known / unknown Mann-Whitney tests "
+                   "(<study>_rank_tests.csv and the two tables)")
     a = p.parse_args(argv)
     logging.basicConfig(level=logging.INFO, format="%(levelname)s %(message)s")
     device = F_.argparse_device(p, a.device)
     if len(a.checkpoint_paths) > MAX_MODELS:
         p.error(f"at most {MAX_MODELS} checkpoints")
     res = compare_checkpoints(a.checkpoint_paths, a.processed_dir, batch_size=a.batch_size, precision=a.precision,
-                              study_name=a.study_name, jobid=a.jobid, output_dir=a.output_dir, metrics_json=a.metrics_json, device=device)
+                              study_name=a.study_name, jobid=a.jobid, output_dir=a.output_dir, metrics_json=a.metrics_json, device=device,
+                              rank_tests=a.rank_tests)
     for path in res["report_paths"]:
         print(f"Full evaluation report saved to {path}")
     print(f"Paired tests saved to {res['tests_path']}")
+    if a.rank_tests:
+        from .rank_tests import format_tables
+        print(f"Rank tests saved to {res['rank_tests_path']}")
     if len(res["names"]) == 1:
         print(format_interpretation(res["table"], res["names"][0], res["channels"]))
+        if a.rank_tests:
+            print(format_tables(res["rank_tests"], res["names"], res["axis_ranges"]))
         return 0
     print(format_table(res["tests"], res["names"]))
     print("\n--- Global summary (all groups): mean (std) ---")
     for g in global_summary(res["table"], res["names"], res["channels"]):
         if g["metric"] in ("mae", "rmse"):
             print(f"{g['model']:<40} {g['channel']:<15} {g['metric']:<5} n={g['n']:<6} {g['mean']:.4f} ({g['std']:.4f})")
+    if a.rank_tests:
+        print(format_tables(res["rank_tests"], res["names"], res["axis_ranges"]))
     return 0
 
 
