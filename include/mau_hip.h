@@ -131,6 +131,14 @@ int mau_conv3x3_first_rows(int N, int H, int W);
 size_t mau_conv3x3_first_wgrad_ws_elems(int N, int H, int W, int Cout);
 int mau_conv3x3_first_wgrad(const void* x8, const void* dz, int lddz, float* dw_oihw, float* ws, int Cin, int Cout, int dtype, int N,
                             int H, int W, mau_stream_t stream);
+/* The same weight gradient with dz formed inside the kernel (loss.backward() through conv0_0's first BatchNorm + ReLU into its
+ * convolution, src/train.py:252 with src/model.py:12,19-20,222): dz = mau_bn_relu_bwd_apply(da, z, ...) is never written -- this layer's
+ * input needs no gradient, so the weight gradient is dz's only reader.  da (N,H,W,ldda), z (N,H,W,ldz) in `dtype`; scale, shift, mean,
+ * invstd, sums, count exactly as mau_bn_relu_bwd_apply takes them (count = 0: the count is sums[2 * Cout]).  dw has EXACTLY the bits
+ * of mau_bn_relu_bwd_apply followed by mau_conv3x3_first_wgrad; same workspace.  Additive to ABI 5. */
+int mau_conv3x3_first_wgrad_bn(const void* x8, const void* da, int ldda, const void* z, int ldz, const float* scale, const float* shift,
+                               const float* mean, const float* invstd, const double* sums, double count, float* dw_oihw, float* ws,
+                               int Cin, int Cout, int dtype, int N, int H, int W, mau_stream_t stream);
 int mau_conv3x3_first_fwd(const float* x_nchw, int Cin, const float* w_oihw, const float* bias, const float* post_scale,
                           const float* post_shift, void* y, int ldy, int Cout, float* slab, void* x8, int dtype, int N, int H,
                           int W, mau_stream_t stream);

@@ -45,6 +45,7 @@ PROTOTYPES = {
     "mau_conv3x3_first_rows": (_i, [_i, _i, _i]),
     "mau_conv3x3_first_wgrad_ws_elems": (_sz, [_i, _i, _i, _i]),
     "mau_conv3x3_first_wgrad": (_i, [_p, _p, _i, _p, _p, _i, _i, _i, _i, _i, _i, _p]),
+    "mau_conv3x3_first_wgrad_bn": (_i, [_p, _p, _i, _p, _i, _p, _p, _p, _p, _p, _d, _p, _p, _i, _i, _i, _i, _i, _i, _p]),
     "mau_conv3x3_first_fwd": (_i, [_p, _i, _p, _p, _p, _p, _p, _i, _i, _p, _p, _i, _i, _i, _i, _p]),
     "mau_conv3x3_fwd": (_i, [_p, _i, _i, _p, _p, _i, _p, _p, _p, _p, _p, _i, _i, _p, _i, _i, _i, _i, _p]),
     "mau_conv3x3_fwd_pool": (_i, [_p, _i, _i, _p, _p, _p, _p, _p, _i, _i, _p, _i, _i, _i, _i, _i, _p]),

@@ -10,6 +10,7 @@
 // per train step of the U-Net).  Hand-off protocol: cdna_hip_programming.md Guideline 16 (agent-scope release / acquire).
 // All of these kernels are HBM-streaming: 16-byte (bf16) / 32-byte (f32) vectors per lane.
 #include <stdlib.h>
+#include "bn_bwd_apply.h"
 #include "mau_common.h"
 
 namespace mau {
@@ -487,32 +488,13 @@ __global__ __launch_bounds__(256) void bn_relu_bwd_apply_kernel(const T* __restr
   const int nv = C8 >> 3;
   const PixVec m(nv);
   if (m.ps >= m.PS) return;
-  if (inv_count <= 0.0) inv_count = 1.0 / sums[2 * C];   // data parallel: all-reduced pixel count appended to the sums
+  inv_count = bn_bwd_inv_count(sums, inv_count, C);
   const int64_t p0 = (int64_t)blockIdx.x * pixb;
   const int64_t p1 = p0 + pixb < npix ? p0 + pixb : npix;
   for (int vv = m.v; vv < nv; vv += m.nvl) {
     const int c = vv * 8;
-    // dy = sc*(dz - m1 - xhat*m2), xhat = (y - mu)*is   ==>   dy = sc*dz - k0 - k1*y
-    float sc[8], sh[8], k0[8], k1[8];
-    double d1[8], d2[8];
-#pragma unroll
-    for (int j = 0; j < 8; ++j) {                        // all 48 loads first, no wait between them (mau_common.h: coef)
-      sc[j] = coef(scale, c + j, C);
-      sh[j] = coef(shift, c + j, C);
-      k0[j] = coef(mean, c + j, C);
-      k1[j] = coef(invstd, c + j, C);
-      d1[j] = coef(sums, c + j, C);
-      d2[j] = coef(sums + C, c + j, C);
-    }
-#pragma unroll
-    for (int j = 0; j < 8; ++j) {
-      const float mu = k0[j], is = k1[j];
-      const float m1 = (float)(d1[j] * inv_count), m2 = (float)(d2[j] * inv_count);
-      // (every product rounded on its own, the difference one explicit FMA: the generic and the fused apply kernels must agree
-      //  to the bit -- left to the compiler, "a*b - c*d" contracts differently from kernel to kernel, visible in fp16 outputs)
-      k1[j] = __fmul_rn(__fmul_rn(sc[j], m2), is);
-      k0[j] = fmaf(sc[j], m1, -__fmul_rn(k1[j], mu));
-    }
+    Apply8 k;                                            // (bn_bwd_apply.h: the one copy of this pass's rounding)
+    k.load(scale, shift, mean, invstd, sums, inv_count, c, C);
     int64_t pix = p0 + m.ps;
     for (; pix + 3 * m.PS < p1; pix += 4 * m.PS) {          // 8 independent 16-byte loads in flight per lane
       F8 g[4], v[4];
@@ -525,11 +507,7 @@ __global__ __launch_bounds__(256) void bn_relu_bwd_apply_kernel(const T* __restr
       for (int u = 0; u < 4; ++u) {
         F8 o;
 #pragma unroll
-        for (int j = 0; j < 8; ++j) {
-          const float act = fmaf(v[u].v[j], sc[j], sh[j]);
-          const float dz = act > 0.f ? g[u].v[j] : 0.f;
-          o.v[j] = fmaf(sc[j], dz, -fmaf(k1[j], v[u].v[j], k0[j]));
-        }
+        for (int j = 0; j < 8; ++j) o.v[j] = k.dy(j, v[u].v[j], g[u].v[j]);
         if (NT) store8_nt<T>(dy + (pix + u * m.PS) * lddy + c, o); else store8<T>(dy + (pix + u * m.PS) * lddy + c, o);
       }
     }
@@ -538,11 +516,7 @@ __global__ __launch_bounds__(256) void bn_relu_bwd_apply_kernel(const T* __restr
       const F8 v = load8<T>(y + pix * ldy + c);
       F8 o;
 #pragma unroll
-      for (int j = 0; j < 8; ++j) {
-        const float act = fmaf(v.v[j], sc[j], sh[j]);
-        const float dz = act > 0.f ? g.v[j] : 0.f;
-        o.v[j] = fmaf(sc[j], dz, -fmaf(k1[j], v.v[j], k0[j]));
-      }
+      for (int j = 0; j < 8; ++j) o.v[j] = k.dy(j, v.v[j], g.v[j]);
       store8<T>(dy + pix * lddy + c, o);
     }
   }

@@ -15,6 +15,7 @@
 // head_bwd_kernel): (8 channel vectors) x (32 pixel slots, stride 32) over BWD_PIX_PER_BLOCK consecutive pixels, and they round
 // the recomputed da / a to the activation type as the unfused path's stores do -- their sums are BIT-IDENTICAL to the unfused
 // path's (tests/test_gpu_ops.py::test_fused_bn_backward_matches_unfused).
+#include "bn_bwd_apply.h"
 #include "mau_common.h"
 
 namespace mau {
@@ -196,38 +197,6 @@ __global__ __launch_bounds__(256) void pool_bn_bwd_reduce_kernel(const T* __rest
   bn_sums_to_slab(red, s1, s2, cv, ps, slab, ldslab);
 }
 
-// k0/k1 of dy = sc*dz - k0 - k1*y (bn_relu_bwd_apply_kernel's form)
-struct Apply8 {
-  float sc[8], sh[8], k0[8], k1[8];
-  __device__ __forceinline__ void load(const float* scale, const float* shift, const float* mean, const float* invstd, const double* sums,
-                                       double inv_count, int c0, int C) {
-    double d1[8], d2[8];
-#pragma unroll
-    for (int j = 0; j < 8; ++j) {                        // all 48 loads first, no wait between them
-      sc[j] = coef(scale, c0 + j, C);
-      sh[j] = coef(shift, c0 + j, C);
-      k0[j] = coef(mean, c0 + j, C);
-      k1[j] = coef(invstd, c0 + j, C);
-      d1[j] = coef(sums, c0 + j, C);
-      d2[j] = coef(sums + C, c0 + j, C);
-    }
-#pragma unroll
-    for (int j = 0; j < 8; ++j) {
-      const float mu = k0[j], is = k1[j];
-      const float m1 = (float)(d1[j] * inv_count), m2 = (float)(d2[j] * inv_count);
-      // (every product rounded on its own, the difference one explicit FMA: the generic and the fused apply kernels must agree
-      //  to the bit -- left to the compiler, "a*b - c*d" contracts differently from kernel to kernel, visible in fp16 outputs)
-      k1[j] = __fmul_rn(__fmul_rn(sc[j], m2), is);
-      k0[j] = fmaf(sc[j], m1, -__fmul_rn(k1[j], mu));
-    }
-  }
-  __device__ __forceinline__ float dy(int j, float yv, float da) const {
-    const float act = fmaf(yv, sc[j], sh[j]);
-    const float dz = act > 0.f ? da : 0.f;
-    return fmaf(sc[j], dz, -fmaf(k1[j], yv, k0[j]));
-  }
-};
-
 // ---- pool: backward pass 2; one thread = a column of RY 2x2 windows x 8 channels (the four y vectors of a window serve arg-max
 // and dy alike; the per-channel coefficients are set up once per thread) ----
 template <typename T, bool POOL, bool SKIP>
@@ -243,7 +212,7 @@ __global__ __launch_bounds__(256) void pool_bn_bwd_apply_kernel(const T* __restr
   if (idx >= Wc * nv) return;
   const int xo = idx / nv, c = (idx - xo * nv) * 8;
   const int n = blockIdx.z;
-  if (inv_count <= 0.0) inv_count = 1.0 / sums[2 * C];
+  inv_count = bn_bwd_inv_count(sums, inv_count, C);
   Apply8 k;
   k.load(scale, shift, mean, invstd, sums, inv_count, c, C);
   const int x0 = 2 * xo;
@@ -568,7 +537,7 @@ __global__ __launch_bounds__(256) void head_bn_bwd_apply_kernel(const T* __restr
   const int cv = threadIdx.x & 7, ps = threadIdx.x >> 3;
   const int c0 = cv * 8;
   if (c0 >= ((C + 7) & ~7)) return;                        // (heads narrower than 64 channels; no barrier below)
-  if (inv_count <= 0.0) inv_count = 1.0 / sums[2 * C];
+  inv_count = bn_bwd_inv_count(sums, inv_count, C);
   Apply8 k;
   k.load(scale, shift, mean, invstd, sums, inv_count, c0, C);
   float wr[MC][8];

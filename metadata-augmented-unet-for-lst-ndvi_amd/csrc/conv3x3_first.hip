@@ -17,6 +17,7 @@
 //   BN sums  : per-lane fp32 running sums (its 16 channels) over every pixel the workgroup processes, reduced across lanes and
 //              waves ONCE at the end: one slab row per workgroup (fixed order: bitwise reproducible)
 //   by-product (training): the converted input as an NHWC-8 tensor for the weight-gradient kernel (x8), written from the halo pass
+#include "bn_bwd_apply.h"
 #include "igemm_bf16_util.h"
 
 namespace mau {
@@ -372,6 +373,14 @@ int mau_conv3x3_first_fwd(const float* x, int Cin, const float* w, const float* 
 //     per halo row; the junk halves are never summed
 //   * 96 accumulator registers; the four waves of a workgroup add up through LDS (fixed order), one compact slab
 //     [workgroup][64][80] fp32, a second kernel adds the slabs in workgroup order and writes OIHW: bitwise reproducible
+//
+// BN form (mau_conv3x3_first_wgrad_bn): dZ is the BatchNorm + ReLU backward's apply pass of (da, z), a tensor with no other reader --
+// this layer's input needs no gradient.  Instead of four dZ DMAs a lane loads its four 16-byte chunks of da and of z into registers,
+// applies the apply pass's expression (bn_bwd_apply.h: the same bits) and writes the results to the offsets the DMAs would have
+// written: 268 MB less written by the apply kernel, 268 MB less read here, one launch less.  Everything behind the LDS image -- the
+// fragments, the MFMA order, the sums -- is the same code.  Vector-memory order per tile: 8 register loads, then the 3 X DMAs; the loads
+// of the NEXT tile are issued before the current one is multiplied, and every wait on them is counted (the loads are inline asm: the
+// compiler would wait vmcnt(0) at the first use of a plain load while a DMA is in flight).
 namespace mau {
 namespace firstw {
 using namespace igemm;
@@ -392,6 +401,14 @@ struct WP {
   float* ws;           // [gridDim.x][gridDim.y * 64][NCOL]
   int N, H, W, tilesX, nTiles;
 };
+struct BNArgs {          // BN form: dz = apply(da, z); dz / lddz of WP are unused
+  const void* da;
+  const void* z;
+  int ldda, ldz;
+  const float *scale, *shift, *mean, *invstd;
+  const double* sums;
+  double inv_count;
+};
 
 template <bool F16>
 __device__ __forceinline__ void mfma(const u32x4& a, const u32x4& b, f32x4v& c) {
@@ -410,8 +427,34 @@ __device__ __forceinline__ u32x4 tr_frag(unsigned addr_lo, unsigned addr_hi) {
   return __builtin_shufflevector(lo, hi, 0, 1, 2, 3);
 }
 
+// four 16-byte register loads at one per-lane address each; their results are NOT ready until load_land()
+__device__ __forceinline__ void load4(u32x4 (&r)[4], const unsigned long long (&a)[4]) {
+#pragma unroll
+  for (int d = 0; d < 4; ++d) asm volatile("global_load_dwordx4 %0, %1, off" : "=&v"(r[d]) : "v"(a[d]) : "memory");
+}
+// "at most N vector-memory operations issued after these eight loads are still in flight": the loads have landed.  (Placed at the END of
+// a trip, so that no load result crosses the loop's back edge unlanded: a register copy the allocator puts there is harmless.)
+template <int N>
+__device__ __forceinline__ void load_land(u32x4 (&g)[4], u32x4 (&v)[4]) {
+  asm volatile("s_waitcnt vmcnt(%8)" : "+v"(g[0]), "+v"(g[1]), "+v"(g[2]), "+v"(g[3]), "+v"(v[0]), "+v"(v[1]), "+v"(v[2]), "+v"(v[3]) : "n"(N) : "memory");
+}
 template <bool F16>
-__global__ __launch_bounds__(NT, 2) void first_wgrad_kernel(WP p) {
+__device__ __forceinline__ F8 unpack8(const u32x4& r) {              // (load8's conversions)
+  F8 o;
+  if constexpr (F16) {
+    const f16x8 a = __builtin_bit_cast(f16x8, r);
+#pragma unroll
+    for (int i = 0; i < 8; ++i) o.v[i] = opaque((float)a[i]);
+  } else {
+    const bf16x8 a = __builtin_bit_cast(bf16x8, r);
+#pragma unroll
+    for (int i = 0; i < 8; ++i) o.v[i] = (float)a[i];
+  }
+  return o;
+}
+
+template <bool F16, bool BN>
+__global__ __launch_bounds__(NT, 2) void first_wgrad_kernel(WP p, BNArgs bn) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];     // NWAVE x 2 x BUF, later the cross-wave sum
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -426,9 +469,9 @@ __global__ __launch_bounds__(NT, 2) void first_wgrad_kernel(WP p) {
   // per-lane constants of the DMAs: dZ DMA d (0..3) covers pixels 8d .. 8d+7, lane = (pixel % 8) * 8 + 16-byte chunk; X halo DMA: lane = halo column
   const int dz_px = lane >> 3, dz_ch = lane & 7;
   const bool dz_ch_ok = co0 + 8 * dz_ch < p.lddz;                          // (narrow layers: the row holds fewer than 64 channels)
-  auto issue = [&](int tile, int buf) {
+  auto issue_dz = [&](int tile, int buf) {
     const int txi = tile % p.tilesX, rowi = tile / p.tilesX;               // rowi = n * H + y
-    const int x0 = txi * TWW, y = rowi % p.H;
+    const int x0 = txi * TWW;
     unsigned char* dst = smem + wave * (2 * BUF) + buf * BUF;
 #pragma unroll
     for (int d = 0; d < 4; ++d) {
@@ -438,6 +481,11 @@ __global__ __launch_bounds__(NT, 2) void first_wgrad_kernel(WP p) {
       src = (gx < p.W && dz_ch_ok) ? src : zero_a;
       __builtin_amdgcn_global_load_lds((glb_ptr)src, (lds_ptr)(dst + d * 1024), 16, 0, 0);
     }
+  };
+  auto issue_x = [&](int tile, int buf) {
+    const int txi = tile % p.tilesX, rowi = tile / p.tilesX;
+    const int x0 = txi * TWW, y = rowi % p.H;
+    unsigned char* dst = smem + wave * (2 * BUF) + buf * BUF;
 #pragma unroll
     for (int dy = 0; dy < 3; ++dy) {
       const int gy = y + dy - 1, gx = x0 + lane - 1;
@@ -447,6 +495,47 @@ __global__ __launch_bounds__(NT, 2) void first_wgrad_kernel(WP p) {
       src = in ? src : zero_a;
       __builtin_amdgcn_global_load_lds((glb_ptr)src, (lds_ptr)(dst + DZ_BYTES + dy * XROW), 16, 0, 0);
     }
+  };
+  // ---- BN form: the lane's chunk is 8 fixed channels -> their coefficients live in registers; rg / rv = the tile's da / z chunks ----
+  Apply8 k;
+  u32x4 rg[4], rv[4];
+  const unsigned long long da_a = (unsigned long long)bn.da, z_a = (unsigned long long)bn.z;
+  if constexpr (BN) k.load(bn.scale, bn.shift, bn.mean, bn.invstd, bn.sums, bn_bwd_inv_count(bn.sums, bn.inv_count, p.Cout), co0 + 8 * dz_ch, p.Cout);
+  auto load_dz = [&](int tile) {                         // 8 register loads; out-of-image lanes and chunks past the row read the zero page
+    const int txi = tile % p.tilesX, rowi = tile / p.tilesX;
+    const int x0 = txi * TWW;
+    unsigned long long ga[4], va[4];
+#pragma unroll
+    for (int d = 0; d < 4; ++d) {
+      const int gx = x0 + 8 * d + dz_px;
+      const unsigned long long pix = (unsigned long long)((long long)rowi * p.W + gx);
+      ga[d] = da_a + 2ull * (pix * (unsigned)bn.ldda + (unsigned)(co0 + 8 * dz_ch));
+      va[d] = z_a + 2ull * (pix * (unsigned)bn.ldz + (unsigned)(co0 + 8 * dz_ch));
+      asm volatile("" : "+v"(ga[d]), "+v"(va[d]));
+      const bool in = gx < p.W && dz_ch_ok;
+      ga[d] = in ? ga[d] : zero_a;
+      va[d] = in ? va[d] : zero_a;
+    }
+    load4(rg, ga);
+    load4(rv, va);
+  };
+  auto commit_dz = [&](int tile, int buf) {              // registers -> the [32 px][64 co] LDS image, zeros where the DMA form reads the zero page
+    const int x0 = (tile % p.tilesX) * TWW;
+    u32x4 o[4];
+#pragma unroll
+    for (int d = 0; d < 4; ++d) {
+      const F8 g = unpack8<F16>(rg[d]), v = unpack8<F16>(rv[d]);
+      F8 r;
+#pragma unroll
+      for (int j = 0; j < 8; ++j) r.v[j] = k.dy(j, v.v[j], g.v[j]);
+      const u32x4 pk = __builtin_bit_cast(u32x4, Lp8<std::conditional_t<F16, f16, bf16>>::from(r));
+      const bool in = x0 + 8 * d + dz_px < p.W && dz_ch_ok;
+#pragma unroll
+      for (int i = 0; i < 4; ++i) o[d][i] = in ? pk[i] : 0u;
+    }
+    // (one statement, closed by idle cycles: the compiler does not see these stores and may re-use o[] right behind them)
+    asm volatile("ds_write_b128 %0, %1\n\tds_write_b128 %0, %2 offset:1024\n\tds_write_b128 %0, %3 offset:2048\n\tds_write_b128 %0, %4 offset:3072\n\ts_nop 1"
+                 :: "v"(lds0 + buf * BUF + lane * 16), "v"(o[0]), "v"(o[1]), "v"(o[2]), "v"(o[3]) : "memory");
   };
   // per-lane LDS read addresses (relative to a buffer).  Lane l: K block g = l / 16 (pixels 8g .. 8g+7), i = l % 16 -> row q = i / 4 of
   // the 4-pixel block, column quad pq = i % 4.
@@ -466,11 +555,32 @@ __global__ __launch_bounds__(NT, 2) void first_wgrad_kernel(WP p) {
 
   const int nw = gridDim.x * NWAVE, w0 = blockIdx.x * NWAVE + wave;
   int buf = 0;
-  if (w0 < p.nTiles) issue(w0, 0);
+  if (w0 < p.nTiles) {
+    if constexpr (BN) {
+      load_dz(w0);
+      issue_x(w0, 0);
+      load_land<3>(rg, rv);
+    } else {
+      issue_dz(w0, 0);
+      issue_x(w0, 0);
+    }
+  }
   for (int tile = w0; tile < p.nTiles; tile += nw) {
     const bool more = tile + nw < p.nTiles;
-    if (more) {
-      issue(tile + nw, buf ^ 1);
+    if constexpr (BN) {
+      // in flight here: this tile's 3 X DMAs.  Its da / z chunks are in registers (landed): form dz, free the registers, refill them
+      commit_dz(tile, buf);
+      if (more) {
+        load_dz(tile + nw);
+        issue_x(tile + nw, buf ^ 1);
+        wait_vmcnt<8 + 3>();                             // behind this tile's X DMAs: the 8 loads and 3 DMAs just issued
+      } else {
+        wait_vmcnt<0>();
+      }
+      asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");  // the dz image is written before this wave's transposed reads of it
+    } else if (more) {
+      issue_dz(tile + nw, buf ^ 1);
+      issue_x(tile + nw, buf ^ 1);
       wait_vmcnt<NDMA>();                                // the NDMA just issued may be in flight; this tile's have landed
     } else {
       wait_vmcnt<0>();
@@ -487,6 +597,9 @@ __global__ __launch_bounds__(NT, 2) void first_wgrad_kernel(WP p) {
 #pragma unroll
       for (int j = 0; j < NBT; ++j) mfma<F16>(A[t], B[j], acc[t][j]);
     // (the fragments are in registers: the buffer may be refilled by the DMAs issued at the top of the next trip)
+    if constexpr (BN) {
+      if (more) load_land<3>(rg, rv);                    // the next tile's chunks; its X DMAs stay in flight
+    }
     buf ^= 1;
   }
   wait_vmcnt<0>();
@@ -550,6 +663,30 @@ static int grid_x(int nTiles) {
   const int need = ceil_div(nTiles, NWAVE);
   return need < cap ? need : cap;
 }
+
+// both forms: the persistent kernel (one slab per workgroup), then the sum of the slabs in workgroup order
+template <bool BN>
+static int launch(WP p, const BNArgs& bn, float* dw, int Cin, int dtype, mau_stream_t stream) {
+  p.tilesX = ceil_div(p.W, TWW);
+  p.nTiles = p.N * p.H * p.tilesX;
+  const int coTiles = round_up(p.Cout, 64) / 64;
+  const dim3 grid(grid_x(p.nTiles), coTiles);
+  constexpr size_t lds = (size_t)NWAVE * 2 * BUF;
+  static_assert(lds >= 64 * NCOL * sizeof(float), "the cross-wave sum fits the DMA buffers");
+  hipStream_t st = (hipStream_t)stream;
+  if (dtype == MAU_F16) {
+    MAU_LDS_ATTR(lds, &first_wgrad_kernel<true, BN>);
+    MAU_LAUNCH((first_wgrad_kernel<true, BN>), grid, dim3(NT), lds, st, p, bn);
+  } else {
+    MAU_LDS_ATTR(lds, &first_wgrad_kernel<false, BN>);
+    MAU_LAUNCH((first_wgrad_kernel<false, BN>), grid, dim3(NT), lds, st, p, bn);
+  }
+  const int rc = check_launch("first_wgrad_kernel");
+  if (rc != MAU_OK) return rc;
+  MAU_LAUNCH(first_wgrad_sum_kernel, dim3(ceil_div(p.Cout * Cin * 9, SUM_EL)), dim3(SUM_SL * SUM_EL), 0, st, p.ws, (int)grid.x,
+             coTiles, dw, p.Cout, Cin);
+  return check_launch("first_wgrad_sum_kernel");
+}
 }  // namespace firstw
 }  // namespace mau
 
@@ -567,7 +704,7 @@ int mau_conv3x3_first_wgrad(const void* x8, const void* dz, int lddz, float* dw,
   MAU_REQUIRE(Cin >= 1 && Cin <= 8, "conv3x3_first_wgrad: %d input channels (this kernel serves <= 8; use mau_conv3x3_wgrad2)", Cin);
   MAU_REQUIRE(dtype == MAU_BF16 || dtype == MAU_F16, "conv3x3_first_wgrad: 16-bit activation types only");
   MAU_REQUIRE(lddz % 8 == 0 && lddz >= Cout && ((uintptr_t)x8 % 16) == 0 && ((uintptr_t)dz % 16) == 0, "conv3x3_first_wgrad: bad lddz / alignment");
-  firstw::WP p;
+  firstw::WP p{};
   p.x8 = x8;
   p.dz = dz;
   p.lddz = lddz;
@@ -576,25 +713,40 @@ int mau_conv3x3_first_wgrad(const void* x8, const void* dz, int lddz, float* dw,
   p.N = N;
   p.H = H;
   p.W = W;
-  p.tilesX = ceil_div(W, firstw::TWW);
-  p.nTiles = N * H * p.tilesX;
-  const int coTiles = round_up(Cout, 64) / 64;
-  const dim3 grid(firstw::grid_x(p.nTiles), coTiles);
-  constexpr size_t lds = (size_t)firstw::NWAVE * 2 * firstw::BUF;
-  static_assert(lds >= 64 * firstw::NCOL * sizeof(float), "the cross-wave sum fits the DMA buffers");
-  hipStream_t st = (hipStream_t)stream;
-  if (dtype == MAU_F16) {
-    MAU_LDS_ATTR(lds, &firstw::first_wgrad_kernel<true>);
-    MAU_LAUNCH(firstw::first_wgrad_kernel<true>, grid, dim3(firstw::NT), lds, st, p);
-  } else {
-    MAU_LDS_ATTR(lds, &firstw::first_wgrad_kernel<false>);
-    MAU_LAUNCH(firstw::first_wgrad_kernel<false>, grid, dim3(firstw::NT), lds, st, p);
-  }
-  const int rc = check_launch("first_wgrad_kernel");
-  if (rc != MAU_OK) return rc;
-  MAU_LAUNCH(firstw::first_wgrad_sum_kernel, dim3(ceil_div(Cout * Cin * 9, firstw::SUM_EL)), dim3(firstw::SUM_SL * firstw::SUM_EL), 0, st, ws, (int)grid.x,
-             coTiles, dw, Cout, Cin);
-  return check_launch("first_wgrad_sum_kernel");
+  return firstw::launch<false>(p, firstw::BNArgs{}, dw, Cin, dtype, stream);
+}
+
+int mau_conv3x3_first_wgrad_bn(const void* x8, const void* da, int ldda, const void* z, int ldz, const float* scale, const float* shift,
+                               const float* mean, const float* invstd, const double* sums, double count, float* dw, float* ws, int Cin,
+                               int Cout, int dtype, int N, int H, int W, mau_stream_t stream) {
+  using namespace mau;
+  MAU_REQUIRE(x8 && da && z && scale && shift && mean && invstd && sums && dw && ws && N > 0 && H > 0 && W > 0 && Cout > 0 && count >= 0,
+              "conv3x3_first_wgrad_bn: bad arguments");
+  MAU_REQUIRE(Cin >= 1 && Cin <= 8, "conv3x3_first_wgrad_bn: %d input channels (this kernel serves <= 8)", Cin);
+  MAU_REQUIRE(dtype == MAU_BF16 || dtype == MAU_F16, "conv3x3_first_wgrad_bn: 16-bit activation types only");
+  const int C8 = round_up(Cout, 8);                          // (whole 8-channel vectors of da and z are loaded, as the apply pass does)
+  MAU_REQUIRE(ldda % 8 == 0 && ldz % 8 == 0 && ldda >= C8 && ldz >= C8, "conv3x3_first_wgrad_bn: bad ld");
+  MAU_REQUIRE(((uintptr_t)x8 % 16) == 0 && ((uintptr_t)da % 16) == 0 && ((uintptr_t)z % 16) == 0, "conv3x3_first_wgrad_bn: bad alignment");
+  firstw::WP p{};
+  p.x8 = x8;
+  p.lddz = C8;                                               // chunks at or above it are zeros, as channels past a dz row are
+  p.Cout = Cout;
+  p.ws = ws;
+  p.N = N;
+  p.H = H;
+  p.W = W;
+  firstw::BNArgs bn;
+  bn.da = da;
+  bn.z = z;
+  bn.ldda = ldda;
+  bn.ldz = ldz;
+  bn.scale = scale;
+  bn.shift = shift;
+  bn.mean = mean;
+  bn.invstd = invstd;
+  bn.sums = sums;
+  bn.inv_count = count > 0 ? 1.0 / count : 0.0;
+  return firstw::launch<true>(p, bn, dw, Cin, dtype, stream);
 }
 
 }  // extern "C"

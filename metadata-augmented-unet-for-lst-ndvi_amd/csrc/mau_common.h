@@ -82,6 +82,29 @@ __device__ __forceinline__ F8 load8<f16>(const f16* p) {
   for (int i = 0; i < 8; ++i) r.v[i] = opaque((float)a[i]);
   return r;
 }
+// eight fp32 -> one 16-byte vector of the 16-bit activation type: the ONE conversion every store of such a vector applies
+template <typename T>
+struct Lp8;
+template <>
+struct Lp8<bf16> {
+  typedef bf16x8 vec;
+  static __device__ __forceinline__ vec from(const F8& r) {
+    vec a;
+#pragma unroll
+    for (int i = 0; i < 8; ++i) a[i] = (bf16)r.v[i];
+    return a;
+  }
+};
+template <>
+struct Lp8<f16> {
+  typedef f16x8 vec;
+  static __device__ __forceinline__ vec from(const F8& r) {
+    vec a;
+#pragma unroll
+    for (int i = 0; i < 8; ++i) a[i] = (f16)opaque(r.v[i]);
+    return a;
+  }
+};
 template <typename T>
 __device__ __forceinline__ void store8(T* p, const F8& r);
 template <>
@@ -97,18 +120,12 @@ __device__ __forceinline__ void store8<float>(float* p, const F8& r) {
 }
 template <>
 __device__ __forceinline__ void store8<bf16>(bf16* p, const F8& r) {
-  bf16x8 a;
-#pragma unroll
-  for (int i = 0; i < 8; ++i) a[i] = (bf16)r.v[i];
-  *reinterpret_cast<bf16x8*>(p) = a;
+  *reinterpret_cast<bf16x8*>(p) = Lp8<bf16>::from(r);
 }
 
 template <>
 __device__ __forceinline__ void store8<f16>(f16* p, const F8& r) {
-  f16x8 a;
-#pragma unroll
-  for (int i = 0; i < 8; ++i) a[i] = (f16)opaque(r.v[i]);
-  *reinterpret_cast<f16x8*>(p) = a;
+  *reinterpret_cast<f16x8*>(p) = Lp8<f16>::from(r);
 }
 
 // non-temporal (streaming) variants for data touched exactly once by a kernel
@@ -157,18 +174,12 @@ __device__ __forceinline__ void store8_nt<float>(float* p, const F8& r) {
 }
 template <>
 __device__ __forceinline__ void store8_nt<bf16>(bf16* p, const F8& r) {
-  bf16x8 a;
-#pragma unroll
-  for (int i = 0; i < 8; ++i) a[i] = (bf16)r.v[i];
-  __builtin_nontemporal_store(a, reinterpret_cast<bf16x8*>(p));
+  __builtin_nontemporal_store(Lp8<bf16>::from(r), reinterpret_cast<bf16x8*>(p));
 }
 
 template <>
 __device__ __forceinline__ void store8_nt<f16>(f16* p, const F8& r) {
-  f16x8 a;
-#pragma unroll
-  for (int i = 0; i < 8; ++i) a[i] = (f16)opaque(r.v[i]);
-  __builtin_nontemporal_store(a, reinterpret_cast<f16x8*>(p));
+  __builtin_nontemporal_store(Lp8<f16>::from(r), reinterpret_cast<f16x8*>(p));
 }
 
 // Per-channel coefficient of channel c (0 beyond C).  The load is UNCONDITIONAL (clamped index) and the zero a select: written as

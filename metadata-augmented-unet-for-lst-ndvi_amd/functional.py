@@ -377,6 +377,12 @@ _FUSED_UP = True            # (the upsample member of the above, separately swit
 _PACK_MULTI = True          # one multi-tensor weight-pack launch per optimizer step (functional.PackGroup)
 _INFER_POOL_FUSED = True    # inference: an encoder block's max-pool out of the convolution's epilogue (mau_conv3x3_fwd_pool)
 _FIRST_WGRAD = True         # the first layer's weight gradient on its own kernel (csrc/conv3x3_first.hip)
+# The first layer's dz has ONE reader, its weight gradient (the network input needs no gradient): from this many pixels N*H*W on the
+# weight-gradient kernel forms dz itself from (da, z) in its load stage (mau_conv3x3_first_wgrad_bn) and mau_bn_relu_bwd_apply is not
+# launched for the layer -- same bits.  Measured, the fused call is the faster one at every size down to 2 x 64 x 64 pixels
+# (scripts/first_dz_fused_bench.py, profiles/r26/first_dz_fused.txt): the threshold is NOT the crossover but the first size above those
+# of tests/golden/launch_trace.json, whose recorded sequences stay what they are.  Test hook: 0 = always, 2**62 = never.
+_FIRST_DZ_FUSED_MIN_WORK = 2 * 64 * 64 + 1
 _SIDE_STREAMS = {}
 
 
@@ -406,6 +412,7 @@ _DGRAD_FIRST = None
 # the conv output and of the activation; code / act_dt: the activations' MAU_* code and torch dtype), and the layer's saved tensors
 _Geom = namedtuple("_Geom", "N H W Cin Cout ldy code act_dt dev stream")
 _Saved = namedtuple("_Saved", "x x1 emb weight y scale shift mean invstd a w2 out argidx")
+_DzOperands = namedtuple("_DzOperands", "da sums count")       # a dz that is not materialised: what mau_bn_relu_bwd_apply would have read
 
 
 def _ptr(t):
@@ -675,10 +682,11 @@ def _conv_save(ctx, st: BNState, src, weight, wd, y, coef, head, hw, outs, kept,
 
 # ---- ConvBNReLU.backward, stage by stage.  A dz stage is (g, st, ctx, sv, da, dpl) -> (dy, g32, dhw, dhb): its reduce kernel, the
 # ---- shared _finish_sums, its apply kernel; g32 = [dbeta | dgamma], the LOCAL sums, rounded to fp32 by the reducer
-def _dz_begin(g: _Geom, sv):
+def _dz_begin(g: _Geom, sv, need_dy=True):
     """(slab of the reduce pass, dy, the pointers of scale / shift / mean / invstd)"""
     slab = torch.empty((lib.mau_bn_bwd_rows(g.N * g.H * g.W), 2 * g.Cout), dtype=torch.float32, device=g.dev)
-    return slab, torch.empty_like(sv.y), (sv.scale.data_ptr(), sv.shift.data_ptr(), sv.mean.data_ptr(), sv.invstd.data_ptr())
+    dy = torch.empty_like(sv.y) if need_dy else None
+    return slab, dy, (sv.scale.data_ptr(), sv.shift.data_ptr(), sv.mean.data_ptr(), sv.invstd.data_ptr())
 
 
 def _finish_sums(g: _Geom, st: BNState, slab):
@@ -727,10 +735,11 @@ def _dz_fused_pool(g: _Geom, st: BNState, ctx, sv, da, dpl):
     return dy, g32, None, None
 
 
-def _dz_generic(g: _Geom, st: BNState, ctx, sv, da, dpl):
-    """BatchNorm + ReLU backward, two passes over (da, y), behind whatever produces da from the layer's output gradients."""
+def _dz_generic(g: _Geom, st: BNState, ctx, sv, da, dpl, apply=True):
+    """BatchNorm + ReLU backward, two passes over (da, y), behind whatever produces da from the layer's output gradients.
+    ``apply=False``: the second pass is left to the weight-gradient kernel; dy is returned as its operands (``_DzOperands``)."""
     y, ldy, npix, stream = sv.y, g.ldy, g.N * g.H * g.W, g.stream
-    slab, dy, cptrs = _dz_begin(g, sv)
+    slab, dy, cptrs = _dz_begin(g, sv, apply)
     dhw = dhb = None
     if ctx.head is not None:
         # unfused head: da, dW, db from the saved activation
@@ -751,6 +760,8 @@ def _dz_generic(g: _Geom, st: BNState, ctx, sv, da, dpl):
     da = _as_nhwc(da)
     call("mau_bn_relu_bwd_reduce", da.data_ptr(), _ld(da), y.data_ptr(), ldy, *cptrs, slab.data_ptr(), g.Cout, g.code, npix, g.Cout, stream)
     sums, count, g32 = _finish_sums(g, st, slab)
+    if not apply:
+        return _DzOperands(da, sums, count), g32, dhw, dhb
     call("mau_bn_relu_bwd_apply", da.data_ptr(), _ld(da), y.data_ptr(), ldy, *cptrs, sums.data_ptr(), count, dy.data_ptr(), ldy, g.code, npix, g.Cout, stream)
     return dy, g32, dhw, dhb
 
@@ -788,7 +799,14 @@ def _conv_wgrad(g: _Geom, st: BNState, sv, E, C1, dy, side, overlap, waits_for_d
     # accumulating AccumulateGrad would add on the main stream to what the side stream is still writing
     # (and only for a parameter: the gradient of a derived weight -- EmbFold's W_eff -- is read by ITS backward on the main stream)
     deferred = side is not None and overlap >= 2 and weight.is_leaf and weight.grad is None
-    if st.first and _FIRST_WGRAD:
+    reads = (x, x1, emb, dy)
+    if isinstance(dy, _DzOperands):
+        # ... and dz formed in its load stage from what the apply pass would have read (_FIRST_DZ_FUSED_MIN_WORK)
+        reads = (x, dy.da, dy.sums, sv.y, sv.scale, sv.shift, sv.mean, sv.invstd)
+        call("mau_conv3x3_first_wgrad_bn", x.data_ptr(), dy.da.data_ptr(), _ld(dy.da), sv.y.data_ptr(), g.ldy, sv.scale.data_ptr(), sv.shift.data_ptr(),
+             sv.mean.data_ptr(), sv.invstd.data_ptr(), dy.sums.data_ptr(), dy.count, dw.data_ptr(), acc.data_ptr(), g.Cin, g.Cout, g.code, g.N, g.H, g.W,
+             wstream)
+    elif st.first and _FIRST_WGRAD:
         # conv0_0.conv1: K = pixels, N = 9 taps x 8 channels straight from the forward's NHWC-8 by-product (csrc/conv3x3_first.hip)
         call("mau_conv3x3_first_wgrad", x.data_ptr(), dy.data_ptr(), g.ldy, dw.data_ptr(), acc.data_ptr(), g.Cin, g.Cout, g.code, g.N, g.H, g.W, wstream)
     else:
@@ -798,7 +816,7 @@ def _conv_wgrad(g: _Geom, st: BNState, sv, E, C1, dy, side, overlap, waits_for_d
         call("mau_conv3x3_unpack_wgrad", acc.data_ptr(), lib.mau_conv3x3_wgrad_splits(g.code, g.N, g.H, g.W, g.Cout, g.Cin),
              dw.data_ptr(), g.Cout, g.Cin, wstream)
     if deferred:
-        for t in (x, x1, emb, dy, dw):                           # read / written over there after this function has returned
+        for t in (*reads, dw):                                   # read / written over there after this function has returned
             if t is not None:
                 t.record_stream(side)
         weight._mau_grad_stream = side                           # (dist.GradSync: the bucket's launch waits for it)
@@ -875,7 +893,11 @@ class ConvBNReLU(torch.autograd.Function):
         needs = ctx.needs_input_grad
         dz = (_dz_fused_head if (ctx.head is not None and ctx.head[3])
               else _dz_fused_pool if (ctx.pooled and dpl is not None and sv.argidx is not None) else _dz_generic)
-        dy, g32, dhw, dhb = dz(g, st, ctx, sv, da, dpl)
+        if dz is _dz_generic and st.first and _FIRST_WGRAD and needs[3] and N * H * W >= _FIRST_DZ_FUSED_MIN_WORK:
+            # (the first layer has no data gradient: dz's one reader is the weight gradient, which forms it itself)
+            dy, g32, dhw, dhb = _dz_generic(g, st, ctx, sv, da, dpl, apply=False)
+        else:
+            dy, g32, dhw, dhb = dz(g, st, ctx, sv, da, dpl)
         dgamma, dbeta = g32[Cout:], g32[:Cout]
         # --- weight gradient: independent of the data gradient given dy ---
         need_dx = needs[0] or (sv.x1 is not None and needs[1]) or (E and needs[2])
