@@ -11,46 +11,10 @@
 // All of these kernels are HBM-streaming: 16-byte (bf16) / 32-byte (f32) vectors per lane.
 #include <stdlib.h>
 #include "bn_bwd_apply.h"
-#include "mau_common.h"
+#include "bn_bwd_reduce.h"
+#include "bn_stats.h"
 
 namespace mau {
-
-// ---- the fixed-order two-accumulator sum of the reductions below, with a group's loads in flight at once ----
-//     s0 += v[first], v[first + 8], ...;   s1 += v[first + 4], v[first + 12], ...      (indices < end, ascending)
-// is the arithmetic of the plain loop "for (k = first; k + 4 < end; k += 8) { s0 += v[k]; s1 += v[k + 4]; } if (k < end) s0 += v[k];"
-// -- same operands, same order, same bits.  As that loop the level was a chain of dependent round trips (each iteration's
-// loads were issued after the previous iteration's additions: 16 trips of ~0.65 us through L2 for 128 chunks; the finalize
-// launches of the 256^2 / 128^2 layers took 14 us against 5.5 us for the layers with <= 16 chunks).  Here whole groups of 16,
-// then of 4 iterations issue their loads back to back and add in order; what is left (< 4 iterations) runs as the plain loop,
-// so the short reductions of the deep layers execute exactly what they did before.  (A single 16-wide group with clamped
-// indices and predicated additions for every length cost the short ones +3.5 us of instruction issue: 4 waves, one per SIMD.)
-template <int G, typename Load>
-__device__ __forceinline__ void ordered_group(int& k, int end, Load load, double& s0, double& s1) {
-  for (; k + 8 * (G - 1) + 4 < end; k += 8 * G) {          // every index of the group is valid
-    double a[G], b[G];
-#pragma unroll
-    for (int i = 0; i < G; ++i) {
-      a[i] = load(k + 8 * i);
-      b[i] = load(k + 8 * i + 4);
-    }
-#pragma unroll
-    for (int i = 0; i < G; ++i) {
-      s0 += a[i];
-      s1 += b[i];
-    }
-  }
-}
-template <typename Load>
-__device__ __forceinline__ void ordered_pair_sum(int first, int end, Load load, double& s0, double& s1) {
-  int k = first;
-  ordered_group<16>(k, end, load, s0, s1);
-  ordered_group<4>(k, end, load, s0, s1);
-  for (; k + 4 < end; k += 8) {
-    s0 += load(k);
-    s1 += load(k + 4);
-  }
-  if (k < end) s0 += load(k);
-}
 
 // ---- column sums of a row-major slab [rows][ldrow] -> out[M], accumulated in fp64 ----
 // Two levels, both deterministic: level 1 cuts the rows into gridDim.y chunks and writes fp64
@@ -59,19 +23,14 @@ __device__ __forceinline__ void ordered_pair_sum(int first, int end, Load load, 
 template <typename InT, typename OutT>
 __global__ __launch_bounds__(256) void reduce_rows_kernel(const InT* __restrict__ slab, int rows, int M, int ldrow,
                                                           OutT* __restrict__ out, int ldout, float* __restrict__ out32) {
-  __shared__ double part[4][64];
+  __shared__ double part[1][4][64];
   const int col = blockIdx.x * 64 + (threadIdx.x & 63);
   const int rl = threadIdx.x >> 6;
   const int per = (rows + gridDim.y - 1) / gridDim.y;
   const int r0 = blockIdx.y * per, r1 = min(rows, r0 + per);
-  double s0 = 0.0, s1 = 0.0;
-  if (col < M) {
-    if (r0 + rl < r1) ordered_pair_sum(r0 + rl, r1, [&](int r) { return (double)slab[(size_t)r * ldrow + col]; }, s0, s1);
-  }
-  part[rl][threadIdx.x & 63] = s0 + s1;
-  __syncthreads();
+  lane_sums_to_lds<1>(part, col < M, r0, r1, [&](int, int r) { return (double)slab[(size_t)r * ldrow + col]; });
   if (rl == 0 && col < M) {
-    const double v = part[0][threadIdx.x] + part[1][threadIdx.x] + part[2][threadIdx.x] + part[3][threadIdx.x];
+    const double v = join4_chain(part[0], threadIdx.x);
     out[(size_t)blockIdx.y * ldout + col] = (OutT)v;
     if (out32 != nullptr) out32[col] = (float)v;         // (final level only) the same sums rounded to fp32
   }
@@ -107,30 +66,20 @@ template <typename OutT>
 __global__ __launch_bounds__(256) void reduce_rows_fused_kernel(const float* __restrict__ slab, int rows, int M, int ldrow, int split,
                                                                 int gap, double* __restrict__ part, unsigned* __restrict__ tickets,
                                                                 OutT* __restrict__ out, float* __restrict__ out32, double append) {
-  __shared__ double ps[4][64];
+  __shared__ double ps[1][4][64];
   const int cl = threadIdx.x & 63, rl = threadIdx.x >> 6;
   const int j = blockIdx.x * 64 + cl;
   const int col = j < split ? j : j - split + gap;
   const int chunks = gridDim.y;
   const int per = (rows + chunks - 1) / chunks;
   const int r0 = blockIdx.y * per, r1 = min(rows, r0 + per);
-  double s0 = 0.0, s1 = 0.0;
-  if (j < M) {
-    if (r0 + rl < r1) ordered_pair_sum(r0 + rl, r1, [&](int r) { return (double)slab[(size_t)r * ldrow + col]; }, s0, s1);
-  }
-  ps[rl][cl] = s0 + s1;
-  __syncthreads();
-  if (rl == 0 && j < M) part[(size_t)blockIdx.y * M + j] = ps[0][cl] + ps[1][cl] + ps[2][cl] + ps[3][cl];
+  lane_sums_to_lds<1>(ps, j < M, r0, r1, [&](int, int r) { return (double)slab[(size_t)r * ldrow + col]; });
+  if (rl == 0 && j < M) part[(size_t)blockIdx.y * M + j] = join4_chain(ps[0], cl);
   if (!last_block_of(tickets + blockIdx.x, (unsigned)chunks)) return;
   // level 2: the chunks' partials in a fixed order (the order of reduce_rows_kernel<double, OutT> on one chunk)
-  s0 = s1 = 0.0;
-  if (j < M) {
-    if (rl < chunks) ordered_pair_sum(rl, chunks, [&](int k) { return part[(size_t)k * M + j]; }, s0, s1);
-  }
-  ps[rl][cl] = s0 + s1;
-  __syncthreads();
+  lane_sums_to_lds<1>(ps, j < M, 0, chunks, [&](int, int k) { return part[(size_t)k * M + j]; });
   if (rl == 0 && j < M) {
-    const double v = ps[0][cl] + ps[1][cl] + ps[2][cl] + ps[3][cl];
+    const double v = join4_chain(ps[0], cl);
     out[j] = (OutT)v;
     if (out32 != nullptr) out32[j] = (float)v;
   }
@@ -155,20 +104,7 @@ __global__ void bn_finalize_train_kernel(const double* __restrict__ sums, double
   if (c == 0 && nbt) *nbt += 1;
   if (c >= C) return;
   if (count <= 0.0) count = sums[2 * C];              // data parallel: the all-reduced pixel count travels with the sums
-  const double mean = sums[c] / count;
-  double var = sums[C + c] / count - mean * mean;     // biased variance (normalisation)
-  if (var < 0.0) var = 0.0;
-  const float invstd = (float)(1.0 / sqrt(var + (double)eps));
-  const float sc = gamma[c] * invstd;
-  scale[c] = sc;
-  shift[c] = beta[c] - (float)mean * sc;
-  mean_o[c] = (float)mean;
-  invstd_o[c] = invstd;
-  if (rmean) {
-    const double unbiased = count > 1.0 ? var * (count / (count - 1.0)) : var;
-    rmean[c] = (1.f - momentum) * rmean[c] + momentum * (float)mean;
-    rvar[c] = (1.f - momentum) * rvar[c] + momentum * (float)unbiased;
-  }
+  bn_finalize_channel(sums[c], sums[C + c], count, c, gamma, beta, rmean, rvar, momentum, eps, scale, shift, mean_o, invstd_o);
 }
 
 // Fused second level of the statistics reduce + finalize (single-GPU training): partial fp64 sums
@@ -180,35 +116,13 @@ __global__ __launch_bounds__(256) void bn_finalize_from_partials_kernel(const do
                                                  float* __restrict__ rmean, float* __restrict__ rvar, int64_t* nbt, float momentum,
                                                  float eps, float* __restrict__ scale, float* __restrict__ shift,
                                                  float* __restrict__ mean_o, float* __restrict__ invstd_o, int C) {
-  __shared__ double ps[4][64], pq[4][64];
+  __shared__ double ps[2][4][64];                              // [sum | sum of squares]
   const int cl = threadIdx.x & 63, kl = threadIdx.x >> 6;
   const int c = blockIdx.x * 64 + cl;
   if (blockIdx.x == 0 && threadIdx.x == 0 && nbt) *nbt += 1;
-  double s0 = 0.0, q0 = 0.0, s1 = 0.0, q1 = 0.0;
-  if (c < C && kl < chunks) {
-    ordered_pair_sum(kl, chunks, [&](int k) { return part[(size_t)k * 2 * ldp + c]; }, s0, s1);
-    ordered_pair_sum(kl, chunks, [&](int k) { return part[(size_t)k * 2 * ldp + ldp + c]; }, q0, q1);
-  }
-  ps[kl][cl] = s0 + s1;
-  pq[kl][cl] = q0 + q1;
-  __syncthreads();
+  lane_sums_to_lds<2>(ps, c < C, 0, chunks, [&](int q, int k) { return part[(size_t)k * 2 * ldp + q * ldp + c]; });
   if (kl != 0 || c >= C) return;
-  const double s = (ps[0][cl] + ps[1][cl]) + (ps[2][cl] + ps[3][cl]);
-  const double q = (pq[0][cl] + pq[1][cl]) + (pq[2][cl] + pq[3][cl]);
-  const double mean = s / count;
-  double var = q / count - mean * mean;
-  if (var < 0.0) var = 0.0;
-  const float invstd = (float)(1.0 / sqrt(var + (double)eps));
-  const float sc = gamma[c] * invstd;
-  scale[c] = sc;
-  shift[c] = beta[c] - (float)mean * sc;
-  mean_o[c] = (float)mean;
-  invstd_o[c] = invstd;
-  if (rmean) {
-    const double unbiased = count > 1.0 ? var * (count / (count - 1.0)) : var;
-    rmean[c] = (1.f - momentum) * rmean[c] + momentum * (float)mean;
-    rvar[c] = (1.f - momentum) * rvar[c] + momentum * (float)unbiased;
-  }
+  bn_finalize_channel(join4_tree(ps[0], cl), join4_tree(ps[1], cl), count, c, gamma, beta, rmean, rvar, momentum, eps, scale, shift, mean_o, invstd_o);
 }
 
 // Single-launch statistics reduce + finalize (single-GPU training): grid (cpad / 64, chunks); level 1 = the conv epilogue's
@@ -221,51 +135,22 @@ __global__ __launch_bounds__(256) void bn_stats_finalize_fused_kernel(const floa
                                                                       float* __restrict__ rvar, int64_t* nbt, float momentum,
                                                                       float eps, float* __restrict__ scale, float* __restrict__ shift,
                                                                       float* __restrict__ mean_o, float* __restrict__ invstd_o, int C) {
-  __shared__ double ps[4][64], pq[4][64];
+  __shared__ double ps[2][4][64];                              // [sum | sum of squares]
   const int cl = threadIdx.x & 63, kl = threadIdx.x >> 6;
   const int c = blockIdx.x * 64 + cl;                          // (c < cpad always: the slab's pad columns are zeros)
   const int chunks = gridDim.y, ld = 2 * cpad;
   const int per = (rows + chunks - 1) / chunks;
   const int r0 = blockIdx.y * per, r1 = min(rows, r0 + per);
-  double s0 = 0.0, q0 = 0.0, s1 = 0.0, q1 = 0.0;
-  if (r0 + kl < r1) {
-    ordered_pair_sum(r0 + kl, r1, [&](int r) { return (double)slab[(size_t)r * ld + c]; }, s0, s1);
-    ordered_pair_sum(r0 + kl, r1, [&](int r) { return (double)slab[(size_t)r * ld + cpad + c]; }, q0, q1);
-  }
-  ps[kl][cl] = s0 + s1;
-  pq[kl][cl] = q0 + q1;
-  __syncthreads();
+  lane_sums_to_lds<2>(ps, true, r0, r1, [&](int q, int r) { return (double)slab[(size_t)r * ld + q * cpad + c]; });
   if (kl == 0) {
-    part[(size_t)blockIdx.y * ld + c] = ps[0][cl] + ps[1][cl] + ps[2][cl] + ps[3][cl];
-    part[(size_t)blockIdx.y * ld + cpad + c] = pq[0][cl] + pq[1][cl] + pq[2][cl] + pq[3][cl];
+    part[(size_t)blockIdx.y * ld + c] = join4_chain(ps[0], cl);
+    part[(size_t)blockIdx.y * ld + cpad + c] = join4_chain(ps[1], cl);
   }
   if (!last_block_of(tickets + blockIdx.x, (unsigned)chunks)) return;
   if (blockIdx.x == 0 && threadIdx.x == 0 && nbt) *nbt += 1;
-  s0 = q0 = s1 = q1 = 0.0;
-  if (c < C && kl < chunks) {
-    ordered_pair_sum(kl, chunks, [&](int k) { return part[(size_t)k * ld + c]; }, s0, s1);
-    ordered_pair_sum(kl, chunks, [&](int k) { return part[(size_t)k * ld + cpad + c]; }, q0, q1);
-  }
-  ps[kl][cl] = s0 + s1;
-  pq[kl][cl] = q0 + q1;
-  __syncthreads();
+  lane_sums_to_lds<2>(ps, c < C, 0, chunks, [&](int q, int k) { return part[(size_t)k * ld + q * cpad + c]; });
   if (kl != 0 || c >= C) return;
-  const double s = (ps[0][cl] + ps[1][cl]) + (ps[2][cl] + ps[3][cl]);
-  const double q = (pq[0][cl] + pq[1][cl]) + (pq[2][cl] + pq[3][cl]);
-  const double mean = s / count;
-  double var = q / count - mean * mean;
-  if (var < 0.0) var = 0.0;
-  const float invstd = (float)(1.0 / sqrt(var + (double)eps));
-  const float sc = gamma[c] * invstd;
-  scale[c] = sc;
-  shift[c] = beta[c] - (float)mean * sc;
-  mean_o[c] = (float)mean;
-  invstd_o[c] = invstd;
-  if (rmean) {
-    const double unbiased = count > 1.0 ? var * (count / (count - 1.0)) : var;
-    rmean[c] = (1.f - momentum) * rmean[c] + momentum * (float)mean;
-    rvar[c] = (1.f - momentum) * rvar[c] + momentum * (float)unbiased;
-  }
+  bn_finalize_channel(join4_tree(ps[0], cl), join4_tree(ps[1], cl), count, c, gamma, beta, rmean, rvar, momentum, eps, scale, shift, mean_o, invstd_o);
 }
 
 __global__ void bn_coeffs_eval_kernel(const float* __restrict__ gamma, const float* __restrict__ beta,
@@ -421,16 +306,9 @@ __global__ __launch_bounds__(256) void bn_relu_bwd_reduce_kernel(const T* __rest
   const int c0 = blockIdx.y * 64 + cv * 8;
   const int64_t p0 = (int64_t)blockIdx.x * BWD_PIX_PER_BLOCK;
   const int64_t p1 = p0 + BWD_PIX_PER_BLOCK < npix ? p0 + BWD_PIX_PER_BLOCK : npix;
-  float s1[8], s2[8], sc[8], sh[8], mu[8], is[8];
-#pragma unroll
-  for (int j = 0; j < 8; ++j) {
-    s1[j] = s2[j] = 0.f;
-    const int cc = c0 + j;
-    sc[j] = coef(scale, cc, C);
-    sh[j] = coef(shift, cc, C);
-    mu[j] = coef(mean, cc, C);
-    is[j] = coef(invstd, cc, C);
-  }
+  Coef8 k;                                               // (bn_bwd_reduce.h: the one copy of this pass's rounding)
+  k.load<false>(scale, shift, mean, invstd, c0, C);           // (the entry point refuses null moments)
+  float s1[8] = {}, s2[8] = {};
   if (c0 < C) {
     int64_t p = p0 + ps;
     for (; p + 32 < p1; p += 64) {                           // 4 independent 16-byte loads in flight per lane
@@ -441,41 +319,15 @@ __global__ __launch_bounds__(256) void bn_relu_bwd_reduce_kernel(const T* __rest
         v[u] = load8<T>(y + (p + 32 * u) * ldy + c0);
       }
 #pragma unroll
-      for (int u = 0; u < 2; ++u)
-#pragma unroll
-        for (int j = 0; j < 8; ++j) {
-          const float act = fmaf(v[u].v[j], sc[j], sh[j]);
-          const float dz = act > 0.f ? g[u].v[j] : 0.f;
-          s1[j] += dz;
-          s2[j] = fmaf(dz, (v[u].v[j] - mu[j]) * is[j], s2[j]);      // (explicit: the fused forms in bn_fused.hip must round alike)
-        }
+      for (int u = 0; u < 2; ++u) bn_bwd_accumulate8(k, v[u], g[u], s1, s2);
     }
     for (; p < p1; p += 32) {
       const F8 g = load8<T>(da + p * ldda + c0);
       const F8 v = load8<T>(y + p * ldy + c0);
-#pragma unroll
-      for (int j = 0; j < 8; ++j) {
-        const float act = fmaf(v.v[j], sc[j], sh[j]);
-        const float dz = act > 0.f ? g.v[j] : 0.f;
-        s1[j] += dz;
-        s2[j] = fmaf(dz, (v.v[j] - mu[j]) * is[j], s2[j]);
-      }
+      bn_bwd_accumulate8(k, v, g, s1, s2);
     }
   }
-#pragma unroll
-  for (int j = 0; j < 8; ++j) {
-    red[0][ps][cv * 8 + j] = s1[j];
-    red[1][ps][cv * 8 + j] = s2[j];
-  }
-  __syncthreads();
-  if (threadIdx.x < 128) {
-    const int which = threadIdx.x >> 6, c = threadIdx.x & 63;
-    float s = 0.f;
-#pragma unroll 8
-    for (int r = 0; r < 32; ++r) s += red[which][r][c];
-    const int cc = blockIdx.y * 64 + c;
-    if (cc < ldslab) slab[((size_t)blockIdx.x * 2 + which) * ldslab + cc] = s;
-  }
+  bn_sums_to_slab(red, s1, s2, cv, ps, slab, ldslab);
 }
 
 template <typename T, bool NT>
@@ -616,13 +468,13 @@ int mau_bn_relu_apply(const void* y, int ldy, const float* scale, const float* s
                       int64_t npix, int C, mau_stream_t stream) {
   MAU_REQUIRE(y && a && scale && shift && npix > 0 && C > 0, "bn_relu_apply: bad arguments");
   const int C8 = round_up(C, 8);
-  MAU_REQUIRE(ldy % 8 == 0 && lda % 8 == 0 && ldy >= C8 && lda >= C8, "bn_relu_apply: bad ld");
+  MAU_REQUIRE(ld_ok(ldy, C8) && ld_ok(lda, C8), "bn_relu_apply: bad ld");
   // measured (scripts/elementwise_bench.py): the 2M-pixel level-0 tensors stream best with many short workgroups,
   // the smaller ones with few long ones (the per-channel coefficient set-up is paid once per thread)
   const bool big = npix >= (int64_t)1 << 20;
   const int pixb = pixvec_pixels_per_block(C8 / 8, npix, big ? 8 : 32, big ? 2048 : 256);
   // (measured, round 4: walking the tensor from its END right behind the convolution that wrote it -- hoping for Infinity-Cache hits
-  //  on the most recently written 256 MB -- changes nothing: 86 us either way for 2 x 268 MB = 6.2 TB/s, scripts/stream_order_probe.py)
+  //  on the most recently written 256 MB -- changes nothing: 86 us either way for 2 x 268 MB = 6.2 TB/s, EXPERIMENTS.md)
   MAU_DISPATCH_DTYPE(dtype, MAU_LAUNCH(bn_relu_apply_kernel<T>, dim3(ceil_div(npix, pixb)), dim3(256), 0, (hipStream_t)stream,
                                                (const T*)y, ldy, scale, shift, (T*)a, lda, npix, C, C8, pixb));
   return check_launch("bn_relu_apply_kernel");
@@ -632,7 +484,7 @@ int mau_bn_relu_apply_pool(const void* y, int ldy, const float* scale, const flo
                            int ldp, unsigned short* argidx, int dtype, int N, int H, int W, int C, mau_stream_t stream) {
   MAU_REQUIRE(y && a && pooled && scale && shift && N > 0 && H >= 2 && W >= 2 && C > 0, "bn_relu_apply_pool: bad arguments");
   const int C8 = round_up(C, 8);
-  MAU_REQUIRE(ldy % 8 == 0 && lda % 8 == 0 && ldp % 8 == 0 && ldy >= C8 && lda >= C8 && ldp >= C8, "bn_relu_apply_pool: bad ld");
+  MAU_REQUIRE(ld_ok(ldy, C8) && ld_ok(lda, C8) && ld_ok(ldp, C8), "bn_relu_apply_pool: bad ld");
   MAU_REQUIRE((H + 1) / 2 <= 65535 && N <= 65535, "bn_relu_apply_pool: H/2 and N must fit a grid dimension");
   dim3 grid(ceil_div(((W + 1) / 2) * (C8 / 8), 256), (H + 1) / 2, N);
   MAU_DISPATCH_DTYPE(dtype, MAU_LAUNCH(bn_relu_apply_pool_kernel<T>, grid, dim3(256), 0, (hipStream_t)stream, (const T*)y, ldy, scale,
@@ -647,7 +499,7 @@ int mau_bn_relu_bwd_reduce(const void* da, int ldda, const void* y, int ldy, con
                            int C, mau_stream_t stream) {
   MAU_REQUIRE(da && y && scale && shift && mean && invstd && slab && npix > 0 && C > 0, "bn_relu_bwd_reduce: bad arguments");
   const int C8 = round_up(C, 8);                             // (the kernel loads whole 8-channel vectors of da and y)
-  MAU_REQUIRE(ldda % 8 == 0 && ldy % 8 == 0 && ldda >= C8 && ldy >= C8 && ldslab >= C, "bn_relu_bwd_reduce: bad ld");
+  MAU_REQUIRE(ld_ok(ldda, C8) && ld_ok(ldy, C8) && ldslab >= C, "bn_relu_bwd_reduce: bad ld");
   dim3 grid(mau_bn_bwd_rows(npix), ceil_div(C, 64));
   MAU_DISPATCH_DTYPE(dtype, MAU_LAUNCH(bn_relu_bwd_reduce_kernel<T>, grid, dim3(256), 0, (hipStream_t)stream,
                                                (const T*)da, ldda, (const T*)y, ldy, scale, shift, mean, invstd, slab,
@@ -660,7 +512,7 @@ int mau_bn_relu_bwd_apply(const void* da, int ldda, const void* y, int ldy, cons
                           int dtype, int64_t npix, int C, mau_stream_t stream) {
   MAU_REQUIRE(da && y && dy && sums && scale && shift && mean && invstd && npix > 0 && C > 0 && count >= 0, "bn_relu_bwd_apply: bad arguments");
   const int C8 = round_up(C, 8);
-  MAU_REQUIRE(ldda % 8 == 0 && ldy % 8 == 0 && lddy % 8 == 0 && ldda >= C8 && ldy >= C8 && lddy >= C8, "bn_relu_bwd_apply: bad ld");
+  MAU_REQUIRE(ld_ok(ldda, C8) && ld_ok(ldy, C8) && ld_ok(lddy, C8), "bn_relu_bwd_apply: bad ld");
   // up to 64 pixels per thread and as few as 256 workgroups: this kernel's per-channel set-up (6 coefficient vectors,
   // fp64 means) is what the mid-size layers were paying for (C=256: 61 -> 36 us, scripts/elementwise_bench.py)
   const int pixb = pixvec_pixels_per_block(C8 / 8, npix, 64, 256);

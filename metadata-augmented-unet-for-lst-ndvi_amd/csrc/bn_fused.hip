@@ -16,7 +16,8 @@
 // the recomputed da / a to the activation type as the unfused path's stores do -- their sums are BIT-IDENTICAL to the unfused
 // path's (tests/test_gpu_ops.py::test_fused_bn_backward_matches_unfused).
 #include "bn_bwd_apply.h"
-#include "mau_common.h"
+#include "bn_bwd_reduce.h"
+#include "head_shared.h"
 
 namespace mau {
 
@@ -25,14 +26,7 @@ __device__ __forceinline__ float round_to(float v) {
   return opaque((float)(T)opaque(v));          // (a conversion and nothing else: mau_common.h, opaque)
 }
 
-// ---- packed fp32 (v_pk_fma_f32 / v_pk_mul_f32 / v_pk_add_f32 on gfx950): two channels per vector instruction ----
-// Every operation below is the IEEE operation its scalar spelling is (fused multiply-add, multiply, add; conversions per element), so a
-// kernel written on pairs returns the bits of the scalar one -- what it saves is issue slots: the head's backward reduce ran ~215 vector
-// instructions per 8-channel vector (75 of them v_mov shuffling values into and out of the pairs the SLP vectoriser formed), i.e. it was
-// bound by VALU issue (~90 us of pure issue at B = 32 x 256 x 256), not by its 302 MB of traffic.
-typedef float f2 __attribute__((ext_vector_type(2)));
-__device__ __forceinline__ f2 pk_fma(f2 a, f2 b, f2 c) { return __builtin_elementwise_fma(a, b, c); }
-__device__ __forceinline__ f2 splat(float v) { return f2{v, v}; }
+// (pairs of channels, f2: bn_bwd_reduce.h)
 template <typename T>
 __device__ __forceinline__ f2 round_to2(f2 v) {          // round_to<T> of both elements (one v_cvt_pk_* where the type has one)
   if constexpr (sizeof(T) == 4) return v;
@@ -54,20 +48,6 @@ struct P4 {
 #pragma unroll
     for (int i = 0; i < 4; ++i) r.p[i] = f2{v.v[2 * i], v.v[2 * i + 1]};
     return r;
-  }
-};
-
-// coefficients of 8 channels starting at c0 (zeros beyond C)
-struct Coef8 {
-  float sc[8], sh[8], mu[8], is[8];
-  __device__ __forceinline__ void load(const float* scale, const float* shift, const float* mean, const float* invstd, int c0, int C) {
-#pragma unroll
-    for (int j = 0; j < 8; ++j) {
-      sc[j] = coef(scale, c0 + j, C);
-      sh[j] = coef(shift, c0 + j, C);
-      mu[j] = mean ? coef(mean, c0 + j, C) : 0.f;
-      is[j] = invstd ? coef(invstd, c0 + j, C) : 0.f;
-    }
   }
 };
 
@@ -115,25 +95,6 @@ __device__ __forceinline__ F8 pool_eval(const PoolLoads<T>& L) {
   return o;
 }
 
-// the LDS join of bn_relu_bwd_reduce_kernel: 32 pixel slots -> one slab row [2][ldslab] per workgroup
-__device__ __forceinline__ void bn_sums_to_slab(float (*red)[32][64 + 1], const float* s1, const float* s2, int cv, int ps, float* slab,
-                                                int ldslab) {
-#pragma unroll
-  for (int j = 0; j < 8; ++j) {
-    red[0][ps][cv * 8 + j] = s1[j];
-    red[1][ps][cv * 8 + j] = s2[j];
-  }
-  __syncthreads();
-  if (threadIdx.x < 128) {
-    const int which = threadIdx.x >> 6, c = threadIdx.x & 63;
-    float s = 0.f;
-#pragma unroll 8
-    for (int r = 0; r < 32; ++r) s += red[which][r][c];
-    const int cc = blockIdx.y * 64 + c;
-    if (cc < ldslab) slab[((size_t)blockIdx.x * 2 + which) * ldslab + cc] = s;
-  }
-}
-
 // ---- pool: backward pass 1 (partial sums of dz and dz * xhat) ----
 __device__ __forceinline__ void advance32(int& n, int& yi, int& xi, int H, int W) {
   xi += 32;
@@ -162,15 +123,10 @@ __global__ __launch_bounds__(256) void pool_bn_bwd_reduce_kernel(const T* __rest
   float s1[8], s2[8];
 #pragma unroll
   for (int j = 0; j < 8; ++j) s1[j] = s2[j] = 0.f;
-  auto accumulate = [&](const F8& v, const F8& g) {
-#pragma unroll
-    for (int j = 0; j < 8; ++j) {
-      const float act = fmaf(v.v[j], k.sc[j], k.sh[j]);
-      const float dz = act > 0.f ? g.v[j] : 0.f;
-      s1[j] += dz;
-      s2[j] = fmaf(dz, (v.v[j] - k.mu[j]) * k.is[j], s2[j]);
-    }
-  };
+  // Through a lambda on purpose: called directly, the same operations are scheduled differently and the bf16 skip-only form takes
+  // 100 registers instead of 96 -- four waves per SIMD instead of five.  This leans on the compiler's inlining order: after a
+  // compiler update, compare the kernel's register count again.
+  auto accumulate = [&](const F8& v, const F8& g) { bn_bwd_accumulate8(k, v, g, s1, s2); };
   if (c0 < C) {
     int64_t p = p0 + ps;
     const int HW = H * W, nv = (C + 7) >> 3;
@@ -381,7 +337,7 @@ __global__ __launch_bounds__(256, HEAD_WAVES) void head_bn_bwd_reduce_kernel(con
   float* row = head_slab + (size_t)blockIdx.x * rowlen;
   Coef8 k;
   k.load(scale, shift, mean, invstd, c0, C);
-  // (pairs of channels: see "packed fp32" at the top of the file -- same operations, same order, same bits as the scalar spelling)
+  // (pairs of channels: see "packed fp32" in bn_bwd_reduce.h -- same operations, same order, same bits as the scalar spelling)
   f2 sc2[4], sh2[4], mu2[4], is2[4], s1p[4], s2p[4], dwq[MC][4], wq[MC][4];
   float dbp[MC];
 #pragma unroll
@@ -416,9 +372,7 @@ __global__ __launch_bounds__(256, HEAD_WAVES) void head_bn_bwd_reduce_kernel(con
           dwq[o][i] = pk_fma(splat(dz[o]), a, dwq[o][i]);
         }
       const f2 da = round_to2<T>(s);                                             // the gradient head_bwd stored
-      const f2 dzb = f2{act[0] > 0.f ? da[0] : 0.f, act[1] > 0.f ? da[1] : 0.f};
-      s1p[i] += dzb;
-      s2p[i] = pk_fma(dzb, (v.p[i] - mu2[i]) * is2[i], s2p[i]);
+      bn_bwd_accumulate2(act, v.p[i], da, mu2[i], is2[i], s1p[i], s2p[i]);
     }
   };
   // The loop is a software pipeline of depth two: the loads of the NEXT pixel pair (16 bytes of y + the head's out / dout words, per
@@ -592,17 +546,11 @@ __global__ __launch_bounds__(256) void head_bn_bwd_apply_kernel(const T* __restr
 // mau_head_fwd's fast path (head.hip): heads of at most 64 channels on images of at least 32 pixels
 int head_fwd_fast(const void* a, int lda, const float* w, const float* b, float* out, int tanh0, int dtype, int64_t npix, int HW, int C, int Co,
                   hipStream_t stream) {
-  const int pixb = npix >= ((int64_t)1 << 20) ? 1024 : 128;
+  const int pixb = head_fwd_pixb(npix);
   const dim3 grid(ceil_div(npix, pixb));
   const float* none = nullptr;
-#define MAU_HEAD_PLAIN(MC_, EX_)                                                                                                            \
-  MAU_DISPATCH_DTYPE(dtype, MAU_LAUNCH((head_bn_fwd_kernel<T, MC_, EX_, false>), grid, dim3(256), 0, stream, (const T*)a, lda, none, none, w, b, out, \
-                                       tanh0, HW, C, Co, npix, pixb))
-  if (Co == 2) MAU_HEAD_PLAIN(2, true);
-  else if (Co == 1) MAU_HEAD_PLAIN(2, false);
-  else if (Co == HEAD_MAX_CO) MAU_HEAD_PLAIN(HEAD_MAX_CO, true);
-  else MAU_HEAD_PLAIN(HEAD_MAX_CO, false);
-#undef MAU_HEAD_PLAIN
+  MAU_HEAD_DISPATCH(Co, MAU_DISPATCH_DTYPE(dtype, MAU_LAUNCH((head_bn_fwd_kernel<T, MC_, EX_, false>), grid, dim3(256), 0, stream, (const T*)a, lda,
+                                                             none, none, w, b, out, tanh0, HW, C, Co, npix, pixb)));
   return check_launch("head_fwd_kernel");
 }
 
@@ -617,8 +565,7 @@ int mau_pool_bn_bwd_reduce(const void* y, int ldy, const void* dpl, int lddpl, c
                            int W, int C, mau_stream_t stream) {
   MAU_REQUIRE(y && (dpl || dskip) && (!dpl || argidx) && scale && shift && mean && invstd && slab && N > 0 && H >= 2 && W >= 2 && C > 0, "pool_bn_bwd_reduce: bad arguments");
   const int C8 = round_up(C, 8);
-  MAU_REQUIRE(ldy % 8 == 0 && ldy >= C8 && (!dpl || (lddpl % 8 == 0 && lddpl >= C8)) && (!dskip || (lddskip % 8 == 0 && lddskip >= C8)) && ldslab >= C,
-              "pool_bn_bwd_reduce: bad ld");
+  MAU_REQUIRE(ld_ok(ldy, C8) && (!dpl || ld_ok(lddpl, C8)) && (!dskip || ld_ok(lddskip, C8)) && ldslab >= C, "pool_bn_bwd_reduce: bad ld");
   const int64_t npix = (int64_t)N * H * W;
   dim3 grid(ceil_div(npix, BWD_PIX_PER_BLOCK), ceil_div(C, 64));
 #define MAU_POOL_REDUCE(P, S)                                                                                                                  \
@@ -637,8 +584,7 @@ int mau_pool_bn_bwd_apply(const void* y, int ldy, const void* dpl, int lddpl, co
   MAU_REQUIRE(y && (dpl || dskip) && (!dpl || argidx) && dy && sums && scale && shift && mean && invstd && N > 0 && H >= 2 && W >= 2 && C > 0 && count >= 0,
               "pool_bn_bwd_apply: bad arguments");
   const int C8 = round_up(C, 8);
-  MAU_REQUIRE(ldy % 8 == 0 && ldy >= C8 && lddy % 8 == 0 && lddy >= C8 && (!dpl || (lddpl % 8 == 0 && lddpl >= C8)) &&
-                  (!dskip || (lddskip % 8 == 0 && lddskip >= C8)), "pool_bn_bwd_apply: bad ld");
+  MAU_REQUIRE(ld_ok(ldy, C8) && ld_ok(lddy, C8) && (!dpl || ld_ok(lddpl, C8)) && (!dskip || ld_ok(lddskip, C8)), "pool_bn_bwd_apply: bad ld");
   MAU_REQUIRE((H + 1) / 2 <= 65535 && N <= 65535, "pool_bn_bwd_apply: H/2 and N must fit a grid dimension");
   // RY window rows per thread (the coefficient set-up -- 48 loads, fp64 means -- is paid once per thread), as long as >= ~2048 workgroups remain
   const int xb = ceil_div(((W + 1) / 2) * (C8 / 8), 256), Hc = (H + 1) / 2;
@@ -661,22 +607,12 @@ int mau_head_bn_max_channels(void) { return 64; }
 int mau_head_bn_fwd(const void* y, int ldy, const float* scale, const float* shift, const float* w, const float* b, float* out, int tanh0,
                     int dtype, int N, int HW, int C, int Co, mau_stream_t stream) {
   MAU_REQUIRE(y && scale && shift && w && b && out && N > 0 && HW > 0 && C > 0, "head_bn_fwd: bad arguments");
-  MAU_REQUIRE(Co >= 1 && Co <= HEAD_MAX_CO && C <= mau_head_bn_max_channels(), "head_bn_fwd: out_channels in [1,%d], C <= %d", HEAD_MAX_CO,
-              mau_head_bn_max_channels());
-  MAU_REQUIRE(ldy % 8 == 0 && ldy >= round_up(C, 8), "head_bn_fwd: bad ld");
-  MAU_REQUIRE(HW >= 32 && (int64_t)N * HW < ((int64_t)1 << 31), "head_bn_fwd: images of at least 32 pixels, fewer than 2^31 pixels in all");
+  if (const int e = head_bn_check("head_bn_fwd", N, HW, C, Co, ld_ok(ldy, round_up(C, 8)))) return e;
   const int64_t npix = (int64_t)N * HW;
-  const int pixb = npix >= ((int64_t)1 << 20) ? 1024 : 128;
+  const int pixb = head_fwd_pixb(npix);
   const dim3 grid(ceil_div(npix, pixb));
-  // (the reference's head has two outputs: MC = 2 holds half the weight / accumulator registers of the general form; EX: Co == MC)
-#define MAU_HEAD_FWD(MC_, EX_)                                                                                                              \
-  MAU_DISPATCH_DTYPE(dtype, MAU_LAUNCH((head_bn_fwd_kernel<T, MC_, EX_>), grid, dim3(256), 0, (hipStream_t)stream, (const T*)y, ldy, scale, shift, w, b, \
-                                       out, tanh0, HW, C, Co, npix, pixb))
-  if (Co == 2) MAU_HEAD_FWD(2, true);
-  else if (Co == 1) MAU_HEAD_FWD(2, false);
-  else if (Co == HEAD_MAX_CO) MAU_HEAD_FWD(HEAD_MAX_CO, true);
-  else MAU_HEAD_FWD(HEAD_MAX_CO, false);
-#undef MAU_HEAD_FWD
+  MAU_HEAD_DISPATCH(Co, MAU_DISPATCH_DTYPE(dtype, MAU_LAUNCH((head_bn_fwd_kernel<T, MC_, EX_>), grid, dim3(256), 0, (hipStream_t)stream, (const T*)y, ldy,
+                                                             scale, shift, w, b, out, tanh0, HW, C, Co, npix, pixb)));
   return check_launch("head_bn_fwd_kernel");
 }
 
@@ -685,20 +621,12 @@ int mau_head_bn_bwd_reduce(const void* y, int ldy, const float* scale, const flo
                            int dtype, int N, int HW, int C, int Co, mau_stream_t stream) {
   MAU_REQUIRE(y && scale && shift && mean && invstd && w && out && dout && bn_slab && head_slab && N > 0 && HW > 0 && C > 0,
               "head_bn_bwd_reduce: bad arguments");
-  MAU_REQUIRE(Co >= 1 && Co <= HEAD_MAX_CO && C <= mau_head_bn_max_channels(), "head_bn_bwd_reduce: out_channels in [1,%d], C <= %d", HEAD_MAX_CO,
-              mau_head_bn_max_channels());
   const int C8 = round_up(C, 8);
-  MAU_REQUIRE(ldy % 8 == 0 && ldy >= C8 && ldslab >= C, "head_bn_bwd_reduce: bad ld");
-  MAU_REQUIRE(HW >= 32 && (int64_t)N * HW < ((int64_t)1 << 31), "head_bn_bwd_reduce: images of at least 32 pixels, fewer than 2^31 pixels in all");
+  if (const int e = head_bn_check("head_bn_bwd_reduce", N, HW, C, Co, ld_ok(ldy, C8) && ldslab >= C)) return e;
   const int64_t npix = (int64_t)N * HW;
-#define MAU_HEAD_RED(MC_, EX_)                                                                                                              \
-  MAU_DISPATCH_DTYPE(dtype, MAU_LAUNCH((head_bn_bwd_reduce_kernel<T, MC_, EX_>), dim3(ceil_div(npix, BWD_PIX_PER_BLOCK)), dim3(256), 0, (hipStream_t)stream, \
-                                       (const T*)y, ldy, scale, shift, mean, invstd, w, out, dout, bn_slab, ldslab, head_slab, tanh0, HW, C, C8, Co, npix))
-  if (Co == 2) MAU_HEAD_RED(2, true);
-  else if (Co == 1) MAU_HEAD_RED(2, false);
-  else if (Co == HEAD_MAX_CO) MAU_HEAD_RED(HEAD_MAX_CO, true);
-  else MAU_HEAD_RED(HEAD_MAX_CO, false);
-#undef MAU_HEAD_RED
+  MAU_HEAD_DISPATCH(Co, MAU_DISPATCH_DTYPE(dtype, MAU_LAUNCH((head_bn_bwd_reduce_kernel<T, MC_, EX_>), dim3(ceil_div(npix, BWD_PIX_PER_BLOCK)), dim3(256), 0,
+                                                             (hipStream_t)stream, (const T*)y, ldy, scale, shift, mean, invstd, w, out, dout, bn_slab,
+                                                             ldslab, head_slab, tanh0, HW, C, C8, Co, npix)));
   return check_launch("head_bn_bwd_reduce_kernel");
 }
 
@@ -707,23 +635,15 @@ int mau_head_bn_bwd_apply(const void* y, int ldy, const float* scale, const floa
                           int tanh0, int dtype, int N, int HW, int C, int Co, mau_stream_t stream) {
   MAU_REQUIRE(y && scale && shift && mean && invstd && sums && w && out && dout && dy && N > 0 && HW > 0 && C > 0 && count >= 0,
               "head_bn_bwd_apply: bad arguments");
-  MAU_REQUIRE(Co >= 1 && Co <= HEAD_MAX_CO && C <= mau_head_bn_max_channels(), "head_bn_bwd_apply: out_channels in [1,%d], C <= %d", HEAD_MAX_CO,
-              mau_head_bn_max_channels());
   const int C8 = round_up(C, 8);
-  MAU_REQUIRE(ldy % 8 == 0 && ldy >= C8 && lddy % 8 == 0 && lddy >= C8, "head_bn_bwd_apply: bad ld");
-  MAU_REQUIRE(HW >= 32 && (int64_t)N * HW < ((int64_t)1 << 31), "head_bn_bwd_apply: images of at least 32 pixels, fewer than 2^31 pixels in all");
+  if (const int e = head_bn_check("head_bn_bwd_apply", N, HW, C, Co, ld_ok(ldy, C8) && ld_ok(lddy, C8))) return e;
   const int64_t npix = (int64_t)N * HW;
   // 64 (8) pixels per thread: the coefficient set-up is paid once per thread.  (Round 6, same call: 1024 pixels per workgroup 144 us, 2048
   //  131 us, 4096 161 us; the arithmetic on register pairs +-0 -- profiles/r6/head_apply_variants.txt.)
   const int pixb = npix >= ((int64_t)1 << 20) ? 2048 : 256;
-#define MAU_HEAD_APPLY(MC_, EX_)                                                                                                            \
-  MAU_DISPATCH_DTYPE(dtype, MAU_LAUNCH((head_bn_bwd_apply_kernel<T, MC_, EX_>), dim3(ceil_div(npix, pixb)), dim3(256), 0, (hipStream_t)stream, (const T*)y, ldy, \
-                                       scale, shift, mean, invstd, sums, count > 0 ? 1.0 / count : 0.0, w, out, dout, (T*)dy, lddy, tanh0, HW, C, Co, npix, pixb))
-  if (Co == 2) MAU_HEAD_APPLY(2, true);
-  else if (Co == 1) MAU_HEAD_APPLY(2, false);
-  else if (Co == HEAD_MAX_CO) MAU_HEAD_APPLY(HEAD_MAX_CO, true);
-  else MAU_HEAD_APPLY(HEAD_MAX_CO, false);
-#undef MAU_HEAD_APPLY
+  MAU_HEAD_DISPATCH(Co, MAU_DISPATCH_DTYPE(dtype, MAU_LAUNCH((head_bn_bwd_apply_kernel<T, MC_, EX_>), dim3(ceil_div(npix, pixb)), dim3(256), 0,
+                                                             (hipStream_t)stream, (const T*)y, ldy, scale, shift, mean, invstd, sums,
+                                                             count > 0 ? 1.0 / count : 0.0, w, out, dout, (T*)dy, lddy, tanh0, HW, C, Co, npix, pixb)));
   return check_launch("head_bn_bwd_apply_kernel");
 }
 

@@ -2,6 +2,7 @@
 // :187-193), MetadataEncoder MLP (:38-48) and the MSE criterion (src/utils/losses.py:27-39).
 // The head reads NHWC-ld activations and writes the module's NCHW fp32 output directly.
 #include "chunk_reduce.h"
+#include "head_shared.h"
 
 namespace mau {
 
@@ -199,7 +200,7 @@ __global__ __launch_bounds__(256) void head_bwd_kernel(const T* __restrict__ a, 
         store8<T>(da + p * ldda + c0, g8);
       }
     }
-    // reduce the 32 pixel slots through LDS: red[ps][o][64]
+    // reduce the 32 pixel slots through LDS: red[ps][o][64]  (head_bn_bwd_reduce_kernel, bn_fused.hip, repeats this join: keep them in step)
     __syncthreads();
 #pragma unroll
     for (int o = 0; o < HEAD_MAX_CO; ++o)
@@ -446,7 +447,7 @@ int mau_head_fwd(const void* a, int lda, const float* w, const float* b, float* 
                  int C, int Co, mau_stream_t stream) {
   MAU_REQUIRE(a && w && b && out && N > 0 && HW > 0 && C > 0, "head_fwd: bad arguments");
   MAU_REQUIRE(Co >= 1 && Co <= HEAD_MAX_CO, "head_fwd: out_channels must be in [1,%d]", HEAD_MAX_CO);
-  MAU_REQUIRE(lda % 8 == 0 && lda >= round_up(C, 8), "head_fwd: bad ld");
+  MAU_REQUIRE(ld_ok(lda, round_up(C, 8)), "head_fwd: bad ld");
   const int64_t npix = (int64_t)N * HW;
   // heads of at most 64 channels (every model of the reference): four pixels per thread and iteration, no per-pixel division
   // (bn_fused.hip: head_bn_fwd_kernel<..., BN = false>, the same arithmetic in the same order)
@@ -466,7 +467,7 @@ int mau_head_mean(const void* a, int lda, const float* w, const float* b, const 
                   double* ws, unsigned* tickets, int tanh0, int dtype, int N, int HW, int C, int Co, mau_stream_t stream) {
   MAU_REQUIRE(a && w && b && means && ws && tickets && N > 0 && HW > 0 && C > 0, "head_mean: bad arguments");
   MAU_REQUIRE(Co >= 1 && Co <= HEAD_MAX_CO, "head_mean: out_channels must be in [1,%d]", HEAD_MAX_CO);
-  MAU_REQUIRE(lda % 8 == 0 && lda >= round_up(C, 8), "head_mean: bad ld");
+  MAU_REQUIRE(ld_ok(lda, round_up(C, 8)), "head_mean: bad ld");
   MAU_REQUIRE(HW <= (1 << 30), "head_mean: images of at most 2^30 pixels");
   const int bps = ceil_div(HW, HEAD_MEAN_PIX);
   // one ticket per sample (the sweeps run 50 at a time: one launch)
@@ -483,7 +484,7 @@ int mau_head_bwd(const void* a, int lda, const float* w, const float* out, const
   MAU_REQUIRE(a && w && out && dout && da && slab && N > 0 && HW > 0 && C > 0, "head_bwd: bad arguments");
   MAU_REQUIRE(Co >= 1 && Co <= HEAD_MAX_CO, "head_bwd: out_channels must be in [1,%d]", HEAD_MAX_CO);
   const int C8 = round_up(C, 8);
-  MAU_REQUIRE(lda % 8 == 0 && ldda % 8 == 0 && lda >= C8 && ldda >= C8, "head_bwd: bad ld");
+  MAU_REQUIRE(ld_ok(lda, C8) && ld_ok(ldda, C8), "head_bwd: bad ld");
   const int64_t npix = (int64_t)N * HW;
   const size_t lds = (size_t)32 * HEAD_MAX_CO * 65 * sizeof(float);
   MAU_DISPATCH_DTYPE(dtype, MAU_LAUNCH(head_bwd_kernel<T>, dim3(mau_head_bwd_rows(N, HW)), dim3(256), lds, (hipStream_t)stream, (const T*)a, lda, w, out, dout, (T*)da, ldda, slab, tanh0, HW, C, C8, Co, npix));

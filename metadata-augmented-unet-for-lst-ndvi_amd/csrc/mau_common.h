@@ -37,6 +37,8 @@ int check_launch(const char* what);
 
 static inline int ceil_div(int64_t a, int64_t b) { return (int)((a + b - 1) / b); }
 static inline int round_up(int a, int b) { return (a + b - 1) / b * b; }
+// leading dimension of an NHWC-ld tensor read or written as whole 8-channel vectors of C8 = round_up(C, 8) channels
+static inline bool ld_ok(int ld, int C8) { return ld % 8 == 0 && ld >= C8; }
 
 // ---- 8-channel vector access on NHWC-ld tensors (16 B for bf16, 32 B for f32) ----
 struct F8 {

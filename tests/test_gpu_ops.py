@@ -1040,6 +1040,64 @@ def test_bn_stats_finalize_every_length_matches_two_launch_form(mau):
         assert torch.allclose(rv.double(), 0.9 * 1.0 + 0.1 * unbiased.cuda(), rtol=1e-6, atol=0), rows
 
 
+def test_bn_stats_sums_then_finalize_matches_the_single_launch(mau):
+    """The data-parallel forward pair -- mau_bn_stats_sums_f64 (the sums that are all-reduced), then mau_bn_finalize_train -- against
+    mau_bn_stats_finalize_train on the same slab: both finalize through bn_finalize_channel (bn_stats.h), so scale, shift, mean, invstd,
+    the running statistics and num_batches_tracked agree bit for bit.  Integer-valued slab: every sum is exact in any order, only the
+    finalize arithmetic is compared.  C = 70 in cpad = 128: two column blocks, the second partial, through the split / gap column
+    mapping; rows = 1 (one row: the count == 1 branch of the unbiased variance), 33 (one chunk with a tail), 64 (two chunks), 4097 (128
+    chunks).  The count passed as an argument, and count = 0 with the count appended behind the sums.  Nothing is written behind C
+    elements, the tickets are left zeroed."""
+    from mau_amd import functional as F_
+    from mau_amd._lib import call, lib
+    d = torch.device("cuda")
+    st = torch.cuda.current_stream().cuda_stream
+    tk = F_._tickets(d)
+    g = torch.Generator().manual_seed(7)
+    C, cpad, pad = 70, 128, 8
+    gamma = (torch.rand(C, generator=g) + 0.5).cuda()
+    beta = torch.randn(C, generator=g).cuda()
+
+    def fresh():
+        rm, rv = torch.full((C + pad,), float("nan"), device=d), torch.full((C + pad,), float("nan"), device=d)
+        rm[:C], rv[:C] = 0.25, 1.5
+        return [torch.full((C + pad,), float("nan"), device=d) for _ in range(4)] + [rm, rv, torch.zeros((), dtype=torch.int64, device=d)]
+
+    for rows in (1, 33, 64, 4097):
+        slab = torch.zeros(rows, 2 * cpad)
+        slab[:, :C] = torch.randint(-6, 7, (rows, C), generator=g).float()
+        slab[:, cpad:cpad + C] = torch.randint(40, 90, (rows, C), generator=g).float()
+        slab = slab.cuda()
+        count = float(rows)
+        ref = fresh()
+        ws = torch.empty(lib.mau_bn_stats_ws_elems(rows, C), dtype=torch.float64, device=d)
+        call("mau_bn_stats_finalize_train", slab.data_ptr(), rows, count, gamma.data_ptr(), beta.data_ptr(), ref[4].data_ptr(), ref[5].data_ptr(),
+             ref[6].data_ptr(), 0.1, 1e-5, *(o.data_ptr() for o in ref[:4]), ws.data_ptr(), tk.data_ptr(), C, st)
+        for appended in (False, True):
+            out = fresh()
+            sums = torch.full((2 * C + 1 + pad,), float("nan"), dtype=torch.float64, device=d)
+            ws2 = torch.empty(lib.mau_reduce_rows_ws_elems(rows, 2 * C), dtype=torch.float64, device=d)
+            call("mau_bn_stats_sums_f64", slab.data_ptr(), rows, C, sums.data_ptr(), ws2.data_ptr(), tk.data_ptr(), count if appended else 0.0, st)
+            call("mau_bn_finalize_train", sums.data_ptr(), 0.0 if appended else count, gamma.data_ptr(), beta.data_ptr(), out[4].data_ptr(),
+                 out[5].data_ptr(), out[6].data_ptr(), 0.1, 1e-5, *(o.data_ptr() for o in out[:4]), C, st)
+            torch.cuda.synchronize()
+            assert torch.equal(sums[:C], slab[:, :C].double().sum(0)) and torch.equal(sums[C:2 * C], slab[:, cpad:cpad + C].double().sum(0)), rows
+            assert (float(sums[2 * C]) == count) if appended else bool(torch.isnan(sums[2 * C])), (rows, appended)
+            assert bool(torch.isnan(sums[2 * C + 1:]).all()), (rows, appended)
+            for name, a, b in zip(("scale", "shift", "mean", "invstd", "running_mean", "running_var"), out, ref):
+                assert torch.equal(a[:C], b[:C]) and not bool(torch.isnan(a[:C]).any()), (rows, appended, name)
+                assert bool(torch.isnan(a[C:]).all()) and bool(torch.isnan(b[C:]).all()), (rows, appended, name)
+            assert int(out[6]) == 1 and int(ref[6]) == 1
+            # the pair's finalize arithmetic itself, against fp64 (the neighbouring test's tolerances; running_var started at 1.5)
+            m = sums[:C] / count
+            var = (sums[C:2 * C] / count - m * m).clamp_min(0)
+            eps = float(torch.tensor(1e-5, dtype=torch.float32))
+            unbiased = var * count / (count - 1) if count > 1 else var
+            assert torch.allclose(out[0][:C].double(), gamma.double() / torch.sqrt(var + eps), rtol=1e-6, atol=0), (rows, appended)
+            assert torch.allclose(out[5][:C].double(), 0.9 * 1.5 + 0.1 * unbiased, rtol=1e-6, atol=0), (rows, appended)
+    assert int(tk.abs().sum()) == 0                       # every launch left the tickets zeroed
+
+
 @pytest.mark.parametrize("C", [1, 70, 300])
 def test_bn_coeffs_eval_matches_its_definition(mau, C):
     """mau_bn_coeffs_eval against fp64: invstd = 1 / sqrt(running_var + eps), scale = gamma * invstd, shift = beta - running_mean * scale;
