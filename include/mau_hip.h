@@ -155,7 +155,15 @@ int mau_conv3x3_first_fwd(const float* x_nchw, int Cin, const float* w_oihw, con
  *         (app/model_utils.py:102-109, test/evaluate.py:181-186); NULL, NULL = plain convolution;
  *   slab  optional fp32 [num_pixel_tiles][2][Cout64]: per-tile sum / sum of squares of y over the
  *         tile's valid pixels (first half of train-mode nn.BatchNorm2d, src/model.py:13,15).
- * The same entry point computes the data gradient when given dy and the `wd` pack. */
+ * The same entry point computes the data gradient when given dy and the `wd` pack.
+ * Which channels of y a call writes (mau_conv3x3_fwd, _fwd2, _fwd_pool; MAU_F32, MAU_BF16 and MAU_F16 alike): channels [0, Cout) hold
+ * the result, channels [Cout, min(roundup(Cout,64), ldy)) are written as ZERO under every epilogue (the kernels store whole 64-channel
+ * blocks, clipped at ldy), channels behind that and pixels outside the tensor are untouched.  With ldy == roundup(Cout,8) these are
+ * the pad lanes; with ldy > roundup(Cout,8) -- y a channel slot of a wider row buffer -- a call with Cout % 64 != 0 overwrites its
+ * neighbour's first channels, which is why functional.py's out_view demands Cout % 64 == 0.  (tests/test_gpu_conv_pinned.py pins this.)
+ * A source is read in whole 16-channel stages: lanes [C0, min(roundup(C0,16), ldx)) of x must hold finite values (they meet zero
+ * weights: the same test pins that finite values there leave y unchanged; that a NaN there reaches y follows and is not tested);
+ * with C0 % 16 == 0 nothing outside [0, C0) is read. */
 int mau_conv3x3_fwd(const void* x, int ldx, int C0, const float* emb, void* emb_ws, int E, const void* wpk,
                     const float* bias, const float* post_scale, const float* post_shift, void* y, int ldy,
                     int Cout, float* slab, int dtype, int N, int H, int W, mau_stream_t stream);
