@@ -816,6 +816,15 @@ int mau_l1_gradient_loss(const float* out, const float* tgt, double* partial, fl
 size_t mau_ssim_ws_elems(int B, int C, int H, int W);
 int mau_ssim_loss(const float* out, const float* tgt, double* ws, float* per_image, float* loss, int prep, int B, int C,
                   int H, int W, mau_stream_t stream);
+/* The adjoint, for training ON the SSIM term (opt-in; the reference's own criterion detaches it).  Additive to ABI 5.
+ * dout (B,C,H,W) fp32 = scale * d loss / d out, loss being exactly loss[0] of mau_ssim_loss for the same geometry, window and
+ * prep.  EVERY element is written (no pre-zeroed buffer): +0.0 in the rows / columns avg_pool2d drops and, with prep != 0, where
+ * channel 1 lies outside [0, 1] (bounds inclusive, torch.clamp's backward); the prepared channel 0 carries its factor 0.5.  tgt
+ * gets no gradient.  One launch, pixel-owned: a workgroup owns a 16x16 tile of pooled pixels and recomputes the moments of the
+ * 26x26 map pixels that reach it -- no float atomics, the results repeat bit for bit; scale is the last factor applied.
+ * Refusals as in mau_ssim_loss. */
+int mau_ssim_loss_grad(const float* out, const float* tgt, float* dout, float scale, int prep, int B, int C, int H, int W,
+                       mau_stream_t stream);
 
 /* ---- every term of compute_all_loss (src/utils/losses.py:101-115) for one batch in ONE launch: what the validation pass
  *      (src/train.py:20-60) averages.  Value only.  Additive to ABI 5 ----

@@ -6,8 +6,8 @@ contains hyphens).  Importing loads ``libmau_hip.so`` and fails loudly when it i
 from . import _lib                      # noqa: F401  (raises if the HIP library is absent)
 from .model import (MetadataEncoder, TemporalEncoder, UrbanPredictor, UrbanPredictor_unet,  # noqa: F401
                     UrbanPredictor_unetpp, VGGBlock)
-from .losses import (compute_all_loss, compute_loss_l1_grad_ssim, compute_loss_mse, compute_loss_mse_gradient,   # noqa: F401
-                     gradient_loss)
+from .losses import (compute_all_loss, compute_loss_l1_grad_ssim, compute_loss_l1_grad_ssim_trained, compute_loss_mse,   # noqa: F401
+                     compute_loss_mse_gradient, gradient_loss)
 from .inference import GraphedInference  # noqa: F401
 from .train_graph import GraphedTrainStep  # noqa: F401
 from .optim import SGD, Adam, AdamW  # noqa: F401
@@ -32,5 +32,5 @@ def __getattr__(name):
 
 
 __all__ = ["UrbanPredictor", "UrbanPredictor_unet", "UrbanPredictor_unetpp", "VGGBlock", "MetadataEncoder",
-           "TemporalEncoder", "compute_loss_mse", "compute_loss_mse_gradient", "compute_loss_l1_grad_ssim", "compute_all_loss", "gradient_loss",
+           "TemporalEncoder", "compute_loss_mse", "compute_loss_mse_gradient", "compute_loss_l1_grad_ssim", "compute_loss_l1_grad_ssim_trained", "compute_all_loss", "gradient_loss",
            "GraphedInference", "GraphedTrainStep", "AdamW", "Adam", "SGD", "mark_params_updated", *_LAZY_MODULES, *_LAZY_CLASSES]

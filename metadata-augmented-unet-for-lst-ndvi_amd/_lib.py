@@ -166,6 +166,7 @@ PROTOTYPES = {
     "mau_l1_gradient_loss": (_i, [_p, _p, _p, _p, _p, _f, _f, _i, _i, _i, _i, _p]),
     "mau_ssim_ws_elems": (_sz, [_i, _i, _i, _i]),
     "mau_ssim_loss": (_i, [_p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _p]),
+    "mau_ssim_loss_grad": (_i, [_p, _p, _p, _f, _i, _i, _i, _i, _i, _p]),
     "mau_mse_fwd_bwd": (_i, [_p, _p, _p, _p, _p, _i64, _p]),
     "mau_loss_terms_ws_elems": (_sz, [_i, _i, _i, _i]),
     "mau_loss_terms": (_i, [_p, _p, _p, _p, _p, _p, _p, _f, _f, _i, _i, _i, _i, _p]),

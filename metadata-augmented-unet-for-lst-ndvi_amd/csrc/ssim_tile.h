@@ -1,5 +1,5 @@
 // ssim_tile.h -- one 16x16 tile of the SSIM map of one (image, channel) plane, shared by ssim_tiles_kernel (ssim.hip) and
-// loss_terms_kernel (loss_terms.hip): piq.ssim's published defaults (11x11 Gaussian window, sigma 1.5, k1 0.01, k2 0.03, "valid"
+// loss_terms_kernel (loss_terms.hip); its window, geometry and prepared, pooled load also serve ssim_grad_kernel (ssim.hip): piq.ssim's published defaults (11x11 Gaussian window, sigma 1.5, k1 0.01, k2 0.03, "valid"
 // windows, average-pool downsampling by max(1, round(min(H, W) / 256))).  26x26 pooled window in LDS with the reference's channel
 // preparation (src/utils/losses.py:72-84: channel 0 -> (v + 1) / 2, channel 1 -> clamp(v, 0, 1)) applied while loading, separable
 // Gaussian (horizontal pass to LDS, vertical pass in registers) over x, y, x^2, y^2, xy.  No pragma here: the fp32 expressions
@@ -45,19 +45,19 @@ static inline SsimGeometry ssim_geometry(int H, int W) {
   return g;
 }
 
-// The SSIM value of map pixel (ty0 + threadIdx.x / 16, tx0 + threadIdx.x % 16) of the planes ob (output) and tb (target) of
-// channel c, 0.0 outside the Ho x Wo map.  Every thread of the 256-thread workgroup calls it; two barriers inside.
-__device__ __forceinline__ double ssim_tile_value(const float* __restrict__ ob, const float* __restrict__ tb, const SsimW& w, int c,
-                                                  int prep, int ty0, int tx0, int H, int W, int f, int Ho, int Wo) {
-  __shared__ float xs[SS_IN][SS_IN + 1], ys[SS_IN][SS_IN + 1];
-  __shared__ float hz[5][SS_IN][SS_T + 1];
+// The N x N window of prepared, pooled pixels of the planes ob (output) and tb (target) of channel c whose first pixel is (y0, x0)
+// of the Hd x Wd = H/f x W/f pooled image, into xs and ys; 0.0 where the window leaves that image (y0 and x0 may be negative).
+// Every thread of the 256-thread workgroup calls it; no barrier inside.
+template <int N>
+__device__ __forceinline__ void ssim_load_window(float (*xs)[N + 1], float (*ys)[N + 1], const float* __restrict__ ob,
+                                                 const float* __restrict__ tb, int c, int prep, int y0, int x0, int H, int W, int f) {
   const int Hd = H / f, Wd = W / f;
   const float inv = 1.f / (float)(f * f);
-  for (int i = threadIdx.x; i < SS_IN * SS_IN; i += 256) {
-    const int r = i / SS_IN, cc = i % SS_IN;
-    const int y = ty0 + r, x = tx0 + cc;
+  for (int i = threadIdx.x; i < N * N; i += 256) {
+    const int r = i / N, cc = i % N;
+    const int y = y0 + r, x = x0 + cc;
     float xv = 0.f, yv = 0.f;
-    if (y < Hd && x < Wd) {
+    if (y >= 0 && x >= 0 && y < Hd && x < Wd) {
       for (int dy = 0; dy < f; ++dy)
         for (int dx = 0; dx < f; ++dx) {
           float a = ob[(size_t)(y * f + dy) * W + x * f + dx], b = tb[(size_t)(y * f + dy) * W + x * f + dx];
@@ -79,6 +79,15 @@ __device__ __forceinline__ double ssim_tile_value(const float* __restrict__ ob, 
     xs[r][cc] = xv;
     ys[r][cc] = yv;
   }
+}
+
+// The SSIM value of map pixel (ty0 + threadIdx.x / 16, tx0 + threadIdx.x % 16) of the planes ob (output) and tb (target) of
+// channel c, 0.0 outside the Ho x Wo map.  Every thread of the 256-thread workgroup calls it; two barriers inside.
+__device__ __forceinline__ double ssim_tile_value(const float* __restrict__ ob, const float* __restrict__ tb, const SsimW& w, int c,
+                                                  int prep, int ty0, int tx0, int H, int W, int f, int Ho, int Wo) {
+  __shared__ float xs[SS_IN][SS_IN + 1], ys[SS_IN][SS_IN + 1];
+  __shared__ float hz[5][SS_IN][SS_T + 1];
+  ssim_load_window<SS_IN>(xs, ys, ob, tb, c, prep, ty0, tx0, H, W, f);
   __syncthreads();
   for (int i = threadIdx.x; i < SS_IN * SS_T; i += 256) {
     const int r = i / SS_T, cc = i % SS_T;

@@ -1432,3 +1432,31 @@ class L1GradientLoss(torch.autograd.Function):
         if d_l1 is None:
             return None, None
         return g_l1 * d_l1 + g_grad * d_gr, None
+
+
+class SSIMLoss(torch.autograd.Function):
+    """``1 - mean SSIM`` of the prepared maps (src/utils/losses.py:72-97, ``mau_ssim_loss`` with ``prep = 1``) WITH its gradient: the
+    reference detaches this term, ``losses.compute_loss_l1_grad_ssim_trained`` opts in.  The value is the one ``losses.ssim_loss`` returns;
+    ``d loss / d out`` is one pixel-owned launch (``mau_ssim_loss_grad``) made in forward and kept, as ``MSELoss`` keeps its ``dout``."""
+
+    @staticmethod
+    def forward(ctx, out, tgt):
+        _require_cuda(out, "ssim_loss")
+        out = out.contiguous().float()
+        tgt = tgt.contiguous().float()
+        B, Cc, H, W = out.shape
+        ws = torch.empty(lib.mau_ssim_ws_elems(B, Cc, H, W), dtype=torch.float64, device=out.device)
+        per_image = torch.empty(B, dtype=torch.float32, device=out.device)
+        loss = torch.empty(1, dtype=torch.float32, device=out.device)
+        call("mau_ssim_loss", out.data_ptr(), tgt.data_ptr(), ws.data_ptr(), per_image.data_ptr(), loss.data_ptr(), 1, B, Cc, H, W, _stream())
+        dout = torch.empty_like(out) if ctx.needs_input_grad[0] else None
+        if dout is not None:
+            call("mau_ssim_loss_grad", out.data_ptr(), tgt.data_ptr(), dout.data_ptr(), 1.0, 1, B, Cc, H, W, _stream())
+        ctx.save_for_backward(dout)                      # kept across backward calls (retain_graph works)
+        ctx.mark_non_differentiable(per_image)
+        return loss.reshape(()), per_image
+
+    @staticmethod
+    def backward(ctx, g, _g_per_image):
+        (d,) = ctx.saved_tensors
+        return (d * g if d is not None else None), None

@@ -5,18 +5,22 @@
 * ``compute_loss_mse_gradient``   :41-57   mse + 0.1 * gradient
 * ``compute_loss_l1_grad_ssim``   :59-99   l1 + 0.1 * gradient + 0.5 * (1 - ssim)       (the yaml default, conf/config.yaml:42)
 * ``compute_all_loss``            :101-115 every term above, value only                 -> ONE HIP launch (``mau_loss_terms``)
+* ``compute_loss_l1_grad_ssim_trained``    the same values, SSIM attached to the graph   (opt-in, ``train --ssim-gradient``; not in the reference)
 
 In the reference the SSIM values pass through ``torch.Tensor(ssim_vals)`` (:89-96), which detaches them: the SSIM
-term changes the reported number, never the gradient.  ``piq`` (the SSIM provider) is not available in the
+term changes the reported number, never the gradient.  ``compute_loss_l1_grad_ssim`` mirrors that and stays the default.  Whoever
+wants the structural term to shape the forecast asks for it: ``ssim_loss(..., differentiable=True)`` and
+``compute_loss_l1_grad_ssim_trained`` return the same values with ``d ssim / d outputs`` from one pixel-owned HIP launch
+(``mau_ssim_loss_grad``, ``functional.SSIMLoss``), checked against a float64 closed form (``tests/ssim_grad_ref.py``).  ``piq`` (the SSIM provider) is not available in the
 build environment, so the SSIM VALUE follows piq's published default algorithm (11x11 Gaussian, sigma 1.5,
 k1 0.01, k2 0.03, average-pool downsampling by max(1, round(min(H, W)/256))): one fused HIP reduction
 (``mau_ssim_loss``, csrc/ssim.hip), checked on the GPU against the torch-op spelling ``ssim_value_torch`` in ``tests/_helpers.py`` (test infrastructure, not product).
 That scalar is **parity-unpinned** (no reference fixture can be generated without piq); everything that carries
-gradient is pinned by fixture ``g9_losses.npz``.
+gradient in the reference is pinned by fixture ``g9_losses.npz``.
 """
 import torch
 
-from .functional import L1GradientLoss, MSELoss, _require_cuda, _stream, _tickets
+from .functional import L1GradientLoss, MSELoss, SSIMLoss, _require_cuda, _stream, _tickets
 from ._lib import call, lib
 
 
@@ -39,11 +43,14 @@ def compute_loss_mse_gradient(outputs, targets, lambda_grad=0.1):
     return {"total": mse + lambda_grad * g, "mse": mse, "gradient": g}
 
 
-def ssim_loss(outputs, targets):
+def ssim_loss(outputs, targets, differentiable=False):
     """1 - mean over the batch of piq.ssim(prepared outputs, prepared targets) (src/utils/losses.py:72-97) in one HIP
-    reduction; the channel preparation (:72-84) happens while the tiles are loaded.  Value only (no gradient), parity
+    reduction; the channel preparation (:72-84) happens while the tiles are loaded.  Value only (no gradient) as in the
+    reference, unless ``differentiable``: then the same value, attached to ``outputs`` (``functional.SSIMLoss``).  Parity
     unpinned (module docstring).  Returns (loss scalar, per-image SSIM (B,))."""
     _require_cuda(outputs, "compute_loss_l1_grad_ssim")
+    if differentiable:
+        return SSIMLoss.apply(outputs, targets.detach())
     o = outputs.detach().contiguous().float()
     t = targets.detach().contiguous().float()
     B, C, H, W = o.shape
@@ -58,6 +65,15 @@ def compute_loss_l1_grad_ssim(outputs, targets, lambda_grad=0.1, lambda_ssim=0.5
     """src/utils/losses.py:59-99 (same dict keys).  Gradient = d(l1 + lambda_grad*gradient); SSIM is value-only."""
     l1, g = L1GradientLoss.apply(outputs, targets)
     s, _ = ssim_loss(outputs, targets)                                                                     # :72-97
+    total = l1 + lambda_grad * g + lambda_ssim * s
+    return {"total": total, "pixel": l1, "gradient": g, "ssim": s}
+
+
+def compute_loss_l1_grad_ssim_trained(outputs, targets, lambda_grad=0.1, lambda_ssim=0.5):
+    """``compute_loss_l1_grad_ssim`` with the SSIM term attached to the graph: the same dict, the same values, and the gradient
+    d(l1 + lambda_grad*gradient + lambda_ssim*ssim).  Not the reference's behaviour (it detaches the term): opt-in."""
+    l1, g = L1GradientLoss.apply(outputs, targets)
+    s, _ = ssim_loss(outputs, targets, differentiable=True)
     total = l1 + lambda_grad * g + lambda_ssim * s
     return {"total": total, "pixel": l1, "gradient": g, "ssim": s}
 

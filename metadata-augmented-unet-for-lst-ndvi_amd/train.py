@@ -2,6 +2,7 @@
 
     python -m mau_amd.train --device gpu --model-type unet --no-temporal-embeddings --epochs 1 --steps-per-epoch 20
     python -m mau_amd.train --device gpu --model-type unet --no-temporal-embeddings --epochs 1 --processed-dir data/processed
+    python -m mau_amd.train --device gpu --model-type unet --no-temporal-embeddings --epochs 1 --ssim-gradient
 
 The reference wraps the step in Optuna trials, wandb logging and a dataset that is not shipped
 (SURVEY D9); none of that is on the hot path.  This driver keeps: the flags, the study-name suffix
@@ -23,7 +24,7 @@ from typing import Optional
 import torch
 import typer
 
-from . import compute_loss_l1_grad_ssim, compute_loss_mse, compute_loss_mse_gradient
+from . import compute_loss_l1_grad_ssim, compute_loss_l1_grad_ssim_trained, compute_loss_mse, compute_loss_mse_gradient
 from . import data as data_
 from .checkpoint import build_hyperparameters, save_checkpoint
 from .config import CONFIG
@@ -74,7 +75,8 @@ def validate(model: torch.nn.Module, loader, criterion, watchdog=None):
     called as well.  The sums stay on the device and are read back once after the loop.  With a ``watchdog`` the stream is
     synchronised once per batch before ``kick()``: the kick means "the GPU was there"."""
     n_meta = CONFIG.dataset.nb_metadata_features
-    own = {compute_loss_mse: 0, compute_loss_mse_gradient: TERM_MSE_GRADIENT_TOTAL, compute_loss_l1_grad_ssim: ALL_LOSS_TERMS["total"]}
+    own = {compute_loss_mse: 0, compute_loss_mse_gradient: TERM_MSE_GRADIENT_TOTAL, compute_loss_l1_grad_ssim: ALL_LOSS_TERMS["total"],
+           compute_loss_l1_grad_ssim_trained: ALL_LOSS_TERMS["total"]}
     idx = own.get(criterion)
     model.eval()
     acc = other = None
@@ -112,19 +114,20 @@ def main(device: str = "", wandblog: bool = False, n_trials: int = 1, force_stud
          temporal_embeddings: bool = True, metadata_embeddings: bool = True, study_name: str = "urban-predictor",
          model_type: str = "unet++", jobid: str = "", epochs: Optional[int] = None, steps_per_epoch: int = 20,
          precision: str = "bf16", val_batches: int = 2, graph: bool = True, processed_dir: Optional[str] = None,
-         num_workers: int = 0, batch_size: Optional[int] = None):
+         num_workers: int = 0, batch_size: Optional[int] = None, ssim_gradient: bool = False):
     """The reference's CLI (src/train.py:62-73) + --epochs / --steps-per-epoch / --precision / --val-batches / --no-graph /
-    --processed-dir (train on <dir>/train, validate on <dir>/val) / --num-workers / --batch-size."""
+    --processed-dir (train on <dir>/train, validate on <dir>/val) / --num-workers / --batch-size / --ssim-gradient (with the
+    l1-gradient-ssim loss: train on the SSIM term too, which the reference detaches)."""
     return run(device, wandblog, n_trials, force_study_name, temporal_embeddings, metadata_embeddings, study_name, model_type,
                jobid, epochs, steps_per_epoch, precision, val_batches, graph, processed_dir=processed_dir, num_workers=num_workers,
-               batch_size=batch_size)["best"]
+               batch_size=batch_size, ssim_gradient=ssim_gradient)["best"]
 
 
 def run(device: str = "", wandblog: bool = False, n_trials: int = 1, force_study_name: bool = False,
         temporal_embeddings: bool = True, metadata_embeddings: bool = True, study_name: str = "urban-predictor",
         model_type: str = "unet++", jobid: str = "", epochs: Optional[int] = None, steps_per_epoch: int = 20,
         precision: str = "bf16", val_batches: int = 2, graph: bool = True, force_dist: bool = False,
-        processed_dir: Optional[str] = None, num_workers: int = 0, batch_size: Optional[int] = None):
+        processed_dir: Optional[str] = None, num_workers: int = 0, batch_size: Optional[int] = None, ssim_gradient: bool = False):
     """Body of the CLI as a function; returns {'best' (validation loss), 'model', 'optimizer', 'checkpoint_path', 'history',
     'val_terms' (per epoch, the second value of ``validate``), 'step'}.
     ``force_dist``: take the data-parallel path (SyncBN + GradSync over the default process group) even with one rank -- the
@@ -133,12 +136,17 @@ def run(device: str = "", wandblog: bool = False, n_trials: int = 1, force_study
     ``<dir>/train`` (shuffled, RandomFlip) and ``<dir>/val``.  An epoch is then ONE PASS over the train loader and validation runs
     over the whole ``val/`` split: ``steps_per_epoch`` and ``val_batches`` are ignored.  The ragged last batch is not dropped (nor is
     a batch whose time series is padded to another length): the graph is captured for the first full batch's shapes, a batch of
-    other shapes takes the eager step.  ``batch_size`` overrides the yaml value.  One process only."""
+    other shapes takes the eager step.  ``batch_size`` overrides the yaml value.  One process only.
+    ``ssim_gradient``: with ``training.loss == "l1-gradient-ssim"`` the criterion is ``compute_loss_l1_grad_ssim_trained`` (the SSIM
+    term reaches the weights) and the checkpoint's hyperparameters say ``ssim_gradient: True``; any other loss has no SSIM term and
+    is refused.  Off, everything is as the reference has it, the checkpoint's keys included."""
     assert model_type in ["unet", "unet++"], "model_type must be 'unet' or 'unet++'"          # src/train.py:78
     if not force_study_name:                                                                  # src/train.py:79-87
         study_name += "-emb" if temporal_embeddings and metadata_embeddings else "-tempemb" if temporal_embeddings \
             else "-metaemb" if metadata_embeddings else "-noemb"
     typer_device(device)
+    if ssim_gradient and CONFIG.training.loss != "l1-gradient-ssim":                          # before anything touches the GPU
+        raise ValueError(f"--ssim-gradient needs training.loss 'l1-gradient-ssim'; the loss '{CONFIG.training.loss}' has no SSIM term")
     if processed_dir is not None:                    # before anything touches the GPU: a wrong path is the likeliest mistake
         for split in ("train", "val"):
             if not os.path.isdir(os.path.join(processed_dir, split)):
@@ -174,7 +182,7 @@ def run(device: str = "", wandblog: bool = False, n_trials: int = 1, force_study
     elif cfg.loss == "mse-gradient":
         criterion = compute_loss_mse_gradient
     elif cfg.loss == "l1-gradient-ssim":
-        criterion = compute_loss_l1_grad_ssim
+        criterion = compute_loss_l1_grad_ssim_trained if ssim_gradient else compute_loss_l1_grad_ssim
     else:
         raise NotImplementedError(f"Loss {cfg.loss} not implemented.")
     sync = watchdog = None
@@ -191,6 +199,8 @@ def run(device: str = "", wandblog: bool = False, n_trials: int = 1, force_study
             watchdog = CollectiveWatchdog()
     hyper = build_hyperparameters(cfg, model_type, temporal_embeddings, metadata_embeddings,
                                   CONFIG.dataset.input_channels, CONFIG.dataset.target_channels)
+    if ssim_gradient:                                # only then: a checkpoint written without the flag keeps the reference's keys
+        hyper["ssim_gradient"] = True
     gen = torch.Generator().manual_seed(CONFIG.seed + rank)
     # held-out synthetic validation split (the reference's val_loader, src/train.py:183-192): drawn once, from its own generator
     vgen = torch.Generator().manual_seed(CONFIG.seed + 7919 + rank)
