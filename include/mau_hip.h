@@ -626,6 +626,51 @@ int mau_region_gather(const unsigned char* dw_t1, const unsigned char* dw_t2, co
 int mau_region_stitch(const float* win, const int* ys, const int* xs, float* out, int C, int T, int ramp, int Hr, int Wr, int ny, int nx,
                       mau_stream_t stream);
 
+/* ---- placement sweeps: where on a tile does a ph x pw stamp of one land-cover class change the forecast most?  The stamp is written
+ *      into the tile's second class map only (the app's canvas edit changes nothing else, app/processing_utils.py:70-110); its effect
+ *      is the forecast with the stamp minus the forecast of the unedited tile.  ONE launch each.  Additive to ABI 5 ----
+ * mau_placement_pack builds B stamped inputs from ONE resident tile:
+ *   dw_t1, dw_t2 (H,W) uint8 class ids (dw_t2 == NULL: dw_t1); rgb (3,H,W), ndvi (H,W), temp (H,W) fp32 raw, norm 8 fp64 on the
+ *   device: mau_region_gather's planes with Hr, Wr = H, W;
+ *   edits (B,3) int32 ON THE DEVICE, rows of (y0, x0, cls): a captured graph is replayed for the next batch after a device-to-device
+ *   copy of B rows.  Sample b, pixel (y, x): the second class id is cls when 0 <= cls < ncls and y0 <= y < y0 + ph and
+ *   x0 <= x < x0 + pw (evaluated in 64-bit: every int32 is legal), else dw_t2[y, x].  A stamp over an edge is clipped; a stamp
+ *   outside the tile or a cls outside [0, ncls) gives the unedited tile (a baseline sample, the padding of a ragged batch);
+ *   out (B,H,W,ldo) in `dtype`, 16-byte aligned:
+ *     [one-hot dw_t1 (ncls) | rgb (3) | ndvi | temp | one-hot second map (ncls) | zeros up to ldo]
+ *   with mau_scenario_pack's / mau_region_gather's arithmetic exactly (one copy of the per-pixel code).
+ * MAU_ERR_ARG: ph or pw < 1, ncls outside [1, mau_scenario_max_classes()], ldo % 8 != 0 or ldo < 2 ncls + 5, B > 65535,
+ * H * W > 2^30, a NULL required pointer. */
+int mau_placement_pack(const unsigned char* dw_t1, const unsigned char* dw_t2, const float* rgb, const float* ndvi, const float* temp,
+                       const int* edits, const double* norm, void* out, int ldo, int dtype, int B, int H, int W, int ph, int pw, int ncls,
+                       mau_stream_t stream);
+/* mau_placement_result: out (B,2,H,W) fp32 NCHW, the head's output of the B samples; base (2,H,W) fp32, the head's output of the
+ * unedited tile; edits as above (only y0, x0 are read: the stamp's rectangle, whatever its class); roi (H,W) uint8, nonzero =
+ * inside, or NULL.  Per pixel, for out and base alike, t = fl32(fl32(o1 * fl32(temp_std)) + fl32(temp_mean)) (mau_scenario_result's
+ * two roundings, never an FMA); dT = fl32(t - t_base), dN = fl32(o0 - b0).
+ *   rows (B, mau_placement_row_elems() = 12) fp64:
+ *     [0] pixels of the stamp inside the tile   [1] mean dT over the tile   [2] min dT   [3] max dT
+ *     [4] mean dT inside the stamp (NaN when [0] == 0)   [5] mean dT outside it (NaN when the stamp covers the tile)
+ *     [6] roi pixels (0 when roi == NULL)   [7] mean dT over the roi (NaN when [6] == 0)
+ *     [8] mean dN over the tile   [9] mean dN inside the stamp (NaN when [0] == 0)   [10] mean dN over the roi (NaN when [6] == 0)
+ *     [11] non-finite values among the sample's two out planes.
+ *   fmin / fmax skip a NaN, the sums carry it.
+ * Sums are fp64 in a fixed order: a workgroup owns 4096 consecutive pixels of ONE sample (mau_placement_chunks(H, W) per sample), a
+ * thread joins its 16 slots in slot order, the 64 lanes by an xor butterfly 32..1, the four waves in wave order, and the workgroup
+ * that draws the sample's last ticket joins the chunks in chunk order -- no float atomics; a row's bits do not depend on B or on the
+ * sample's slot, and repeat.  Slots: when H * W % 4 == 0 and out, base are 16-byte and roi 4-byte aligned, slot 4k + j of thread t
+ * is pixel (k * 256 + t) * 4 + j of the chunk (16-byte loads); otherwise slot k is pixel k * 256 + t (the two forms add in
+ * different orders).  A sum over a subset (stamp, outside, roi) adds +0.0 for a pixel outside the subset.
+ * ws: fp64 workspace of mau_placement_ws_elems(B, H, W) elements; tickets: a ZEROED mau_reduce_tickets_elems() buffer (left zeroed;
+ * see mau_reduce_rows_f64).  One launch per mau_reduce_tickets_elems() samples.
+ * MAU_ERR_ARG: ph or pw < 1, H * W > 2^30, a NULL required pointer. */
+int mau_placement_row_elems(void);
+int mau_placement_chunks(int H, int W);
+size_t mau_placement_ws_elems(int B, int H, int W);
+int mau_placement_result(const float* out, const float* base, const int* edits, const unsigned char* roi, double temp_mean,
+                         double temp_std, double* rows, double* ws, unsigned* tickets, int B, int H, int W, int ph, int pw,
+                         mau_stream_t stream);
+
 /* ---- model comparison: M heads' outputs of ONE tile against one target (the developer app's Model Comparison page,
  *      app_dev/pages/1_Model_Comparison.py with app_dev/app_src/utils.py:170-271), ONE launch each.  Additive to ABI 5 ----
  * mau_compare_result: out (M,2,H,W) fp32 NCHW, the M heads' outputs (channel 0 NDVI, channel 1 normalised temperature);

@@ -139,6 +139,11 @@ PROTOTYPES = {
     "mau_scenario_result": (_i, [_p, _p, _p, _p, _d, _d, _p, _p, _p, _p, _p, _p, _i, _i, _i, _p]),
     "mau_region_gather": (_i, [_p, _p, _p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _i, _i, _p]),
     "mau_region_stitch": (_i, [_p, _p, _p, _p, _i, _i, _i, _i, _i, _i, _i, _p]),
+    "mau_placement_pack": (_i, [_p, _p, _p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _i, _i, _i, _p]),
+    "mau_placement_row_elems": (_i, []),
+    "mau_placement_chunks": (_i, [_i, _i]),
+    "mau_placement_ws_elems": (_sz, [_i, _i, _i]),
+    "mau_placement_result": (_i, [_p, _p, _p, _p, _d, _d, _p, _p, _p, _i, _i, _i, _i, _i, _p]),
     "mau_compare_row_elems": (_i, []),
     "mau_compare_chunks": (_i, [_i, _i]),
     "mau_compare_ws_elems": (_sz, [_i, _i, _i]),
