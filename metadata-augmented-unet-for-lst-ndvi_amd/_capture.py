@@ -1,5 +1,6 @@
-"""What the captured sessions share (``GraphedInference``, ``ScenarioSession``, ``ComparisonSession``, ``RegionSession``): freezing a
-model, the warm-up and capture sequence, and the pinned staging buffer of a host input.  The replay paths stay in the sessions."""
+"""What the captured sessions share (``GraphedInference``, ``ComparisonSession`` and, through ``_tile.TileSession``, ``ScenarioSession``,
+``PlacementSession`` and ``RegionSession``): freezing a model, the warm-up and capture sequence, and the pinned staging buffer of a
+host input.  The replay paths stay in the sessions."""
 from __future__ import annotations
 
 import numpy as np

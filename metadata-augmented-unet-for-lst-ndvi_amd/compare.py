@@ -30,10 +30,9 @@ import torch
 
 from . import functional as F_
 from ._capture import freeze, warm_up_and_capture
+from ._tile import N_CONT, check_metrics, check_ncls, check_palette, norm_row
 from .functional import _dev, call, lib
-from .scenario import _check_metrics, _norm_row, _palette, palette_from_hex
-
-N_CONT = 5               # rgb (3) + ndvi + temperature
+from .scenario import palette_from_hex
 REGIONS = ("tile", "top_left", "top_right", "bottom_left", "bottom_right")
 ENTRIES = ("count", "gt_min", "gt_max", "pred_min", "pred_max", "max_abs_err", "sum_abs_err", "sum_sq_err")
 VIEW_NAMES = ("rgb8", "temp_c", "ndvi", "dw_t1_rgb", "dw_t2_rgb")
@@ -70,7 +69,7 @@ def compare_host(outputs, target, metrics: dict):
     rows (M * 2, 40) float64) as ``mau_compare_result`` lays them out.  The temperature channel is ``x * temp_std + temp_mean`` on
     a float32 array with Python-float scalars (utils.py:260-261), the error ``pred - gt`` (1_Model_Comparison.py:146); minima and
     maxima skip a NaN, the float64 sums carry it; the whole-tile entries are ((TL o TR) o BL) o BR."""
-    _check_metrics(metrics, ("temp_mean", "temp_std"))
+    check_metrics(metrics, ("temp_mean", "temp_std"))
     outputs, target = np.asarray(outputs, dtype=np.float32), np.asarray(target, dtype=np.float32)
     if outputs.ndim != 4 or outputs.shape[1] != 2 or outputs.shape[0] < 1 or target.shape != outputs.shape[1:]:
         raise ValueError(f"compare_host: outputs must be (M, 2, H, W) and target (2, H, W), got {outputs.shape} and {target.shape}")
@@ -94,8 +93,8 @@ def input_views_host(cls_a, cls_b, cont, palette, metrics: dict) -> dict:
     """The page's views of a compact sample (utils.py:224-252): ``rgb8`` (H,W,3) uint8, ``temp_c`` and ``ndvi`` (H,W) float32,
     ``dw_t1_rgb`` and ``dw_t2_rgb`` (H,W,3) uint8.  The colour planes go through float64 (a float32 array times a float64 array),
     are clipped to [0, 255] and truncated; a NaN gives 0; a class id outside the palette gives black."""
-    _check_metrics(metrics, ("rgb_mean", "rgb_std", "temp_mean", "temp_std"))
-    palette = _palette(palette)
+    check_metrics(metrics, ("rgb_mean", "rgb_std", "temp_mean", "temp_std"))
+    palette = check_palette(palette)
     cont = np.asarray(cont, dtype=np.float32)
     cls_a, cls_b = np.asarray(cls_a), np.asarray(cls_b)
     if cont.ndim != 3 or cont.shape[0] != N_CONT or cls_a.shape != cont.shape[1:] or cls_b.shape != cont.shape[1:]:
@@ -211,13 +210,11 @@ class _ViewTables:
     """The device-side constants of ``mau_compare_inputs`` for one (palette, metrics)."""
 
     def __init__(self, palette, metrics: dict, dev):
-        _check_metrics(metrics)
-        palette = _palette(palette)
-        self.ncls = palette.shape[0]
-        if self.ncls > lib.mau_scenario_max_classes():
-            raise ValueError(f"mau_compare_inputs takes at most {lib.mau_scenario_max_classes()} classes, the palette has {self.ncls}")
+        check_metrics(metrics)
+        palette = check_palette(palette)
+        self.ncls = check_ncls(palette.shape[0], "mau_compare_inputs")
         self.palette = torch.from_numpy(palette).to(dev)
-        self.norm = torch.from_numpy(_norm_row(metrics)).to(dev)
+        self.norm = torch.from_numpy(norm_row(metrics)).to(dev)
 
 
 def _input_views(cls_a, cls_b, cont, tb: _ViewTables, out: Optional[InputViews] = None) -> InputViews:
@@ -281,7 +278,7 @@ class ComparisonSession:
         models = list(models)
         if not models:
             raise ValueError("ComparisonSession: at least one model")
-        _check_metrics(metrics, ("temp_mean", "temp_std"))
+        check_metrics(metrics, ("temp_mean", "temp_std"))
         self.names = [str(name) for name, _ in models]
         self.models = [model for _, model in models]
         self.clone_output = clone_output

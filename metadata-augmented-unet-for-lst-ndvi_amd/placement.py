@@ -20,7 +20,6 @@ The host twins (pure numpy) are the product's reference; the order-exact twin of
 """
 from __future__ import annotations
 
-import json
 from typing import Optional, Sequence, Tuple
 
 import numpy as np
@@ -28,10 +27,10 @@ import torch
 
 from . import functional as F_
 from . import scenario as S
-from ._capture import PinnedStage, freeze, warm_up_and_capture
+from ._capture import PinnedStage
+from ._tile import N_CONT, TileSession, check_ld, check_ncls, check_tile, const, norm_row
 from .functional import Act, call, dtype_code, lib, pad8
 
-N_CONT = S.N_CONT
 ROW = 12
 ROW_NAMES = ("stamp_pixels", "mean_dt", "min_dt", "max_dt", "mean_dt_stamp", "mean_dt_outside", "roi_pixels", "mean_dt_roi",
              "mean_dn", "mean_dn_stamp", "mean_dn_roi", "non_finite")
@@ -152,17 +151,10 @@ def result_host(out, base, edits, patch, temp_mean: float, temp_std: float, roi=
 # --------------------------------------------------------------------------- #
 # the two launches
 # --------------------------------------------------------------------------- #
-def _ncls(ncls: int) -> int:
-    ncls = int(ncls)
-    if not 1 <= ncls <= lib.mau_scenario_max_classes():
-        raise ValueError(f"mau_placement_pack takes 1 to {lib.mau_scenario_max_classes()} classes, got {ncls}")
-    return ncls
-
-
 def _edits_dev(edits, dev) -> torch.Tensor:
     if not (isinstance(edits, torch.Tensor) and edits.is_cuda):
         edits = _edit_rows(edits.cpu().numpy() if isinstance(edits, torch.Tensor) else edits)
-    edits = S._const(edits, torch.int32, dev)
+    edits = const(edits, torch.int32, dev)
     if edits.dim() != 2 or edits.shape[1] != 3 or edits.shape[0] < 1:
         raise ValueError(f"edits must be (B, 3) rows of (y0, x0, cls), got {tuple(edits.shape)}")
     if edits.shape[0] > MAX_BATCH:
@@ -187,17 +179,14 @@ def pack(dw_t1, dw_t2, rgb, ndvi, temp, edits, patch, ncls: int, metrics: dict, 
     edge is clipped, a stamp outside the tile or a class outside [0, ncls) gives the unedited tile; ``patch`` is the stamp's edge
     or (ph, pw); ``ld`` (default: 2 ncls + 5 rounded up to 8) is the channel stride.  Bit-identical to ``data.pack_tiles`` on
     ``edited_maps_host`` and ``normalized_planes_host``."""
-    dw_t1, rgb, ndvi, temp = S._tile(dw_t1, rgb, ndvi, temp)
+    dw_t1, rgb, ndvi, temp = check_tile(dw_t1, rgb, ndvi, temp)
     H, W = dw_t1.shape
     if H * W > MAX_PIXELS:
         raise ValueError(f"pack: tiles of at most 2^30 pixels, got {H} x {W}")
     dw_t2 = None if dw_t2 is None else F_._dev(dw_t2, "dw_t2", torch.uint8, (H, W))
-    (ph, pw), ncls = _patch(patch), _ncls(ncls)
-    C = 2 * ncls + N_CONT
-    ld = pad8(C) if ld is None else int(ld)
-    if ld % 8 or ld < C:
-        raise ValueError(f"pack: ld must be a multiple of 8 and at least {C}, got {ld}")
-    norm = S._const(S._norm_row(metrics), torch.float64, dw_t1.device)
+    (ph, pw), ncls = _patch(patch), check_ncls(ncls, "mau_placement_pack")
+    ld = check_ld(ld, 2 * ncls + N_CONT, "pack")
+    norm = const(norm_row(metrics), torch.float64, dw_t1.device)
     return _pack(dw_t1, dw_t2, rgb, ndvi, temp, _edits_dev(edits, dw_t1.device), norm, ph, pw, ncls, dtype, ld)
 
 
@@ -259,7 +248,7 @@ class PlacementResult:
         return int(self.ys[iy]), int(self.xs[ix]), float(g[iy, ix])
 
 
-class PlacementSession:
+class PlacementSession(TileSession):
     """``PlacementSession(model, dw_t1, rgb, ndvi, temp, metadata, temp_series, metrics=...)(classes, stride=None) -> PlacementResult``.
 
     The tile (device tensors: dw_t1 (H,W) uint8; rgb (3,H,W), ndvi (H,W), temp (H,W) fp32, raw values), the metadata row (1,F) and
@@ -278,48 +267,28 @@ class PlacementSession:
 
     def __init__(self, model: torch.nn.Module, dw_t1, rgb, ndvi, temp, metadata, temp_series, *, metrics: dict, ncls: int = 9,
                  patch=(32, 32), batch: int = 8, dw_t2=None, roi=None, precision: Optional[str] = None, graph: bool = True, warmup: int = 2):
-        dw_t1, rgb, ndvi, temp = S._tile(dw_t1, rgb, ndvi, temp)
-        for t, what in ((metadata, "metadata"), (temp_series, "temp_series")):
-            F_._require_cuda(t, f"PlacementSession({what})")
-        S._check_metrics(metrics)
-        dev = dw_t1.device
-        H, W = dw_t1.shape
         B = int(batch)
         if not 1 <= B <= MAX_BATCH:
             raise ValueError(f"batch must be in [1, {MAX_BATCH}], got {batch}")
-        if H * W > MAX_PIXELS:
-            raise ValueError(f"PlacementSession: tiles of at most 2^30 pixels, got {H} x {W}")
-        self.patch, self.ncls, self.batch, self.shape = _patch(patch), _ncls(ncls), B, (H, W)
-        if self.patch[0] > H or self.patch[1] > W:
-            raise ValueError(f"PlacementSession: a stamp of {self.patch} does not fit a tile of {H} x {W}")
-        if precision is not None:
-            model.set_precision(precision)
-        self.model = model
-        self.dtype = freeze(model)
-        self._tile = tuple(t.detach().clone() for t in (dw_t1, rgb, ndvi, temp))
-        self._dw_t2 = None if dw_t2 is None else F_._dev(dw_t2, "dw_t2", torch.uint8, (H, W)).detach().clone()
-        self._roi = None if roi is None else F_._dev(roi, "roi", torch.uint8, (H, W)).detach().clone()
-        self._norm = S._const(S._norm_row(metrics), torch.float64, dev)
-        self._mean, self._std = float(metrics["temp_mean"]), float(metrics["temp_std"])
-        self._md = metadata.detach().float().reshape(1, -1).expand(B, -1).contiguous()
-        self._ts = temp_series.detach().float().reshape(1, -1).expand(B, -1).contiguous()
+        self.patch, self.ncls = _patch(patch), check_ncls(ncls, "mau_placement_pack")
+        super().__init__(model, dw_t1, rgb, ndvi, temp, metadata, temp_series, metrics, B, precision=precision, dw_t2=dw_t2, roi=roi)
         self._no_edit = np.tile(np.array([[0, 0, NO_EDIT]], dtype=np.int32), (B, 1))
-        self._edits = S._const(self._no_edit, torch.int32, dev)
-        self._base = torch.zeros((2, H, W), dtype=torch.float32, device=dev)
+        self._edits = const(self._no_edit, torch.int32, self._device)
+        self._base = torch.zeros((2, *self.shape), dtype=torch.float32, device=self._device)
         self._stage = PinnedStage((B, 3), torch.int32)                                  # a batch's rows of edits travel through pinned memory
-        # the tickets of the captured reduction are the session's own: a replay never shares them with a launch on another stream
-        self._tickets = torch.zeros(lib.mau_reduce_tickets_elems(), dtype=torch.int32, device=dev)
-        if graph:
-            self.graph, (self._out, self._rows) = warm_up_and_capture(self._run, dev, warmup)
-        else:
-            self.graph = None
-            with torch.no_grad():
-                self._out, self._rows = self._run()
+        self._tickets = self._own_tickets()
+        self._capture(warmup, graph)                                                    # self._out: (the network's output, the rows of figures)
         # the baseline: the same graph, the same batch, no edit
         self._replay()
-        self._base.copy_(self._out[0], non_blocking=True)
-        r = S.result(self._out[:1], None, self._tile[0], self._tile[0][None], self._mean, self._std)
+        self._base.copy_(self.output[0], non_blocking=True)
+        r = S.result(self.output[:1], None, self._tile[0], self._tile[0][None], self._mean, self._std)
         self.ndvi, self.temp_c = r.ndvi[0], r.temp_c[0]
+
+    def _fit(self, H: int, W: int) -> None:
+        if H * W > MAX_PIXELS:
+            raise ValueError(f"PlacementSession: tiles of at most 2^30 pixels, got {H} x {W}")
+        if self.patch[0] > H or self.patch[1] > W:
+            raise ValueError(f"PlacementSession: a stamp of {self.patch} does not fit a tile of {H} x {W}")
 
     def _run(self):
         ld = pad8(2 * self.ncls + N_CONT)
@@ -327,17 +296,10 @@ class PlacementSession:
         out = self.model(x, self._ts, self._md)
         return out, _result(out, self._base, self._edits, self._roi, self._mean, self._std, *self.patch, self._tickets)
 
-    @torch.no_grad()
-    def _replay(self):
-        if self.graph is not None:
-            self.graph.replay()
-        else:
-            self._out, self._rows = self._run()
-
     @property
     def output(self) -> torch.Tensor:
         """The network's output (batch, 2, H, W) fp32 of the last replay: the session's own buffer."""
-        return self._out
+        return self._out[0]
 
     @property
     def base(self) -> torch.Tensor:
@@ -374,7 +336,7 @@ class PlacementSession:
             valid = min(B, K - k0)
             self._stage.upload(np.concatenate([edits[k0:k0 + valid], self._no_edit[valid:]]), self._edits)
             self._replay()
-            table[k0:k0 + valid].copy_(self._rows[:valid], non_blocking=True)
+            table[k0:k0 + valid].copy_(self._out[1][:valid], non_blocking=True)
         return PlacementResult(table.cpu().numpy(), edits, classes, ys, xs, self.ndvi.cpu().numpy(), self.temp_c.cpu().numpy())
 
 
@@ -390,28 +352,13 @@ def _int_list(text: str) -> Sequence[int]:
 
 def run_tile(checkpoint: str, tile: str, metrics_json: str, classes="1,6", patch: int = 32, stride: Optional[int] = None, batch: int = 8,
              roi: str = "", ncls: int = 9, precision: str = "fp16", output: str = "", device: str = "cuda") -> dict:
-    """Body of the CLI: one sweep on the tile of ``tile`` (.npz: dw, rgb, ndvi, temp, metadata_raw = (lat, lon, population,
-    year_t1, month_t1, year_t2, month_t2), optionally dw_t2 and temp_series (raw)); ``roi``: a .npy (H, W) mask.  Returns -- and
-    with ``output`` writes as .npz -- rows, edits, classes, ys, xs, ``grid_c<cls>_e<entry>`` per class for entries 1, 4 and 7,
-    and the unedited forecast ndvi, temp_c."""
-    from .checkpoint import load_model
-    with open(metrics_json) as f:
-        metrics = json.load(f)
-    S._check_metrics(metrics, S.METRIC_KEYS)
+    """Body of the CLI: one sweep on the tile of ``tile`` (.npz: ``scenario.load_tile``'s keys; temp_orig is not used); ``roi``: a
+    .npy (H, W) mask.  Returns -- and with ``output`` writes as .npz -- rows, edits, classes, ys, xs, ``grid_c<cls>_e<entry>`` per
+    class for entries 1, 4 and 7, and the unedited forecast ndvi, temp_c."""
+    t = S.load_tile(tile, metrics_json, device=device, checkpoint=checkpoint, ncls=ncls)
     cls = _int_list(classes) if isinstance(classes, str) else list(classes)
-    d = np.load(tile)
-    md = S.metadata_row(*[float(v) for v in d["metadata_raw"]], metrics["meta_mean"], metrics["meta_std"])
-    ts = S.normalize_temp_series(d["temp_series"], metrics) if "temp_series" in d else np.zeros((1, 60), dtype=np.float32)
-    dw = np.asarray(d["dw"])
-    dw = dw[0] if dw.ndim == 3 else dw
-    H, W = dw.shape
-    model = load_model(checkpoint, device=device, spatial_channels=2 * int(ncls) + N_CONT, seq_len=ts.shape[1])
-    dev = lambda a, dt, shape: torch.from_numpy(np.ascontiguousarray(np.reshape(a, shape), dtype=dt)).to(device)       # noqa: E731
-    mask = (np.load(roi) != 0).astype(np.uint8) if roi else None
-    sess = PlacementSession(model, dev(dw, np.uint8, (H, W)), dev(d["rgb"], np.float32, (3, H, W)), dev(d["ndvi"], np.float32, (H, W)),
-                            dev(d["temp"], np.float32, (H, W)), dev(md, np.float32, md.shape), dev(ts, np.float32, ts.shape), metrics=metrics,
-                            ncls=ncls, patch=patch, batch=batch, dw_t2=dev(d["dw_t2"], np.uint8, (H, W)) if "dw_t2" in d else None,
-                            roi=None if mask is None else dev(mask, np.uint8, (H, W)), precision=precision)
+    mask = torch.from_numpy((np.load(roi) != 0).astype(np.uint8).reshape(tuple(t.dw.shape))).to(device) if roi else None
+    sess = PlacementSession(*t[:7], metrics=t.metrics, ncls=ncls, patch=patch, batch=batch, dw_t2=t.dw_t2, roi=mask, precision=precision)
     r = sess(cls, stride=stride)
     res = {"rows": r.rows, "edits": r.edits, "classes": r.classes, "ys": r.ys, "xs": r.xs, "ndvi": r.ndvi, "temp_c": r.temp_c,
            **{f"grid_c{c}_e{e}": r.grid(c, e) for c in r.classes for e in GRID_ENTRIES}}

@@ -18,7 +18,6 @@ The host twins (pure numpy) are the truth the device path is tested against, bit
 """
 from __future__ import annotations
 
-import json
 from typing import Optional, Tuple
 
 import numpy as np
@@ -26,11 +25,11 @@ import torch
 
 from . import functional as F_
 from . import scenario as S
-from ._capture import PinnedStage, freeze, warm_up_and_capture
+from ._capture import PinnedStage
+from ._tile import N_CONT, TileSession, check_ld, check_ncls, check_palette, check_tile, const, norm_row, upload
 from .config import CONFIG
-from .functional import Act, call, dtype_code, lib, pad8
+from .functional import Act, call, dtype_code, pad8
 
-N_CONT = S.N_CONT
 MAX_WINDOW = 4096
 MAX_COVER = 3            # windows over one coordinate: two of the regular stride (overlap <= T // 2) and the last one, moved back
 
@@ -141,13 +140,6 @@ def stitch_host(win, ys, xs, shape: Tuple[int, int], ramp: int) -> np.ndarray:
 # --------------------------------------------------------------------------- #
 # the two launches
 # --------------------------------------------------------------------------- #
-def _ncls(ncls: int) -> int:
-    ncls = int(ncls)
-    if not 1 <= ncls <= lib.mau_scenario_max_classes():
-        raise ValueError(f"mau_region_gather takes 1 to {lib.mau_scenario_max_classes()} classes, got {ncls}")
-    return ncls
-
-
 def _gather(dw_t1, dw_t2, rgb, ndvi, temp, origins, norm, T: int, ncls: int, dtype: torch.dtype, ld: int) -> Act:
     Hr, Wr = dw_t1.shape
     B = origins.shape[0]
@@ -164,21 +156,18 @@ def gather(dw_t1, dw_t2, rgb, ndvi, temp, origins, window: int, ncls: int, metri
     degrees C, fp32, on the device; ``origins`` (B,2) rows of (y0, x0), a host array or an int32 device tensor, each clamped into
     the region by the kernel; ``ld`` (default: 2 ncls + 5 rounded up to 8) is the channel stride.  Bit-identical to
     ``data.pack_tiles`` on the cropped class maps and ``normalized_planes_host`` of the cropped raw planes."""
-    dw_t1, rgb, ndvi, temp = S._tile(dw_t1, rgb, ndvi, temp)
+    dw_t1, rgb, ndvi, temp = check_tile(dw_t1, rgb, ndvi, temp)
     Hr, Wr = dw_t1.shape
     dw_t2 = dw_t1 if dw_t2 is None else F_._dev(dw_t2, "dw_t2", torch.uint8, (Hr, Wr))
-    T, ncls = int(window), _ncls(ncls)
+    T, ncls = int(window), check_ncls(ncls, "mau_region_gather")
     if not 1 <= T <= min(Hr, Wr, MAX_WINDOW):
         raise ValueError(f"gather: a window of {T} does not fit a region of {Hr} x {Wr} (windows of at most {MAX_WINDOW}); a region "
                          "smaller than a window is one tile: use ScenarioSession")
-    C = 2 * ncls + N_CONT
-    ld = pad8(C) if ld is None else int(ld)
-    if ld % 8 or ld < C:
-        raise ValueError(f"gather: ld must be a multiple of 8 and at least {C}, got {ld}")
-    origins = S._const(origins, torch.int32, dw_t1.device)
+    ld = check_ld(ld, 2 * ncls + N_CONT, "gather")
+    origins = const(origins, torch.int32, dw_t1.device)
     if origins.dim() != 2 or origins.shape[1] != 2 or origins.shape[0] < 1:
         raise ValueError(f"origins must be (B, 2) rows of (y0, x0), got {tuple(origins.shape)}")
-    norm = S._const(S._norm_row(metrics), torch.float64, dw_t1.device)
+    norm = const(norm_row(metrics), torch.float64, dw_t1.device)
     return _gather(dw_t1, dw_t2, rgb, ndvi, temp, origins, norm, T, ncls, dtype, ld)
 
 
@@ -207,7 +196,7 @@ def stitch(win: torch.Tensor, ys, xs, shape: Tuple[int, int], ramp: int) -> torc
     ys, xs = _check_table(ys, Hr, T, "ys"), _check_table(xs, Wr, T, "xs")
     if win.shape[0] != ys.size * xs.size:
         raise ValueError(f"win holds {win.shape[0]} windows, the tables name {ys.size} x {xs.size}")
-    return _stitch(win, S._const(ys, torch.int32, win.device), S._const(xs, torch.int32, win.device), Hr, Wr, ramp)
+    return _stitch(win, const(ys, torch.int32, win.device), const(xs, torch.int32, win.device), Hr, Wr, ramp)
 
 
 # --------------------------------------------------------------------------- #
@@ -223,7 +212,7 @@ class RegionResult(S.ScenarioResult):
         self.output, self.window_outputs = output, window_outputs
 
 
-class RegionSession:
+class RegionSession(TileSession):
     """``RegionSession(model, dw_t1, rgb, ndvi, temp, metadata, temp_series, palette=..., metrics=...)(dw_t2=None) -> RegionResult``.
 
     The region (device tensors: dw_t1 (Hr,Wr) uint8; rgb (3,Hr,Wr), ndvi (Hr,Wr), temp (Hr,Wr) fp32, raw values) stays resident.
@@ -245,77 +234,59 @@ class RegionSession:
     def __init__(self, model: torch.nn.Module, dw_t1, rgb, ndvi, temp, metadata, temp_series, *, palette, metrics: dict,
                  window: int = CONFIG.model.img_size, overlap: Optional[int] = None, batch: int = 8, dw_t2=None, temp_orig=None,
                  warmup: int = 2):
-        dw_t1, rgb, ndvi, temp = S._tile(dw_t1, rgb, ndvi, temp)
-        for t, what in ((metadata, "metadata"), (temp_series, "temp_series")):
-            F_._require_cuda(t, f"RegionSession({what})")
-        S._check_metrics(metrics)
-        dev = dw_t1.device
-        Hr, Wr = dw_t1.shape
-        T, B = int(window), int(batch)
+        if int(batch) < 1:
+            raise ValueError("batch must be >= 1")
+        self.window, self.overlap = int(window), int(window) // 4 if overlap is None else int(overlap)
+        self._ncls = check_ncls(check_palette(palette).shape[0], "mau_region_gather")
+        super().__init__(model, dw_t1, rgb, ndvi, temp, metadata, temp_series, metrics, batch, dw_t2=dw_t2, temp_orig=temp_orig)
+        dev, B = self._device, self.batch
+        if self._dw_t2 is None:                                                         # no land-cover change; a call may replace it
+            self._dw_t2 = self._tile[0].clone()
+        self._ys, self._xs = const(self.ys, torch.int32, dev), const(self.xs, torch.int32, dev)
+        # the origin rows of all windows, padded to whole batches with the last window
+        rows = np.stack([np.repeat(self.ys, self.xs.size), np.tile(self.xs, self.ys.size)], axis=1).astype(np.int32)
+        self._origins_all = const(np.concatenate([rows, np.repeat(rows[-1:], self._batches * B - self.windows, 0)]), torch.int32, dev)
+        self._origins = self._origins_all[:B].clone()
+        self._stage = PinnedStage(self.shape, torch.uint8)                              # a host class map travels through pinned memory
+        self._capture(warmup)
+
+    def _fit(self, Hr: int, Wr: int) -> None:
+        T = self.window
         if T > min(Hr, Wr):
             raise ValueError(f"RegionSession: the region ({Hr} x {Wr}) is smaller than a window ({T}); one tile is ScenarioSession's case")
-        if B < 1:
-            raise ValueError("batch must be >= 1")
-        self.window, self.overlap = T, T // 4 if overlap is None else int(overlap)
         self.ys, self.xs = window_origins(Hr, T, self.overlap), window_origins(Wr, T, self.overlap)
-        self.ramp, self.batch, self.shape = default_ramp(self.overlap), B, (Hr, Wr)
-        ny, nx = self.ys.size, self.xs.size
-        self.windows = nWin = ny * nx
-        self._ncls = _ncls(S._palette(palette).shape[0])
-        self.model = model
-        self.dtype = freeze(model)
-        self._region = tuple(t.detach().clone() for t in (dw_t1, rgb, ndvi, temp))
-        self._dw_t2 = (dw_t1 if dw_t2 is None else F_._dev(dw_t2, "dw_t2", torch.uint8, (Hr, Wr))).detach().clone()
-        self._temp_orig = self._region[3] if temp_orig is None else F_._dev(temp_orig, "temp_orig", torch.float32, (Hr, Wr)).detach().clone()
-        self._norm = S._const(S._norm_row(metrics), torch.float64, dev)
-        self._mean, self._std = float(metrics["temp_mean"]), float(metrics["temp_std"])
-        self._ys, self._xs = S._const(self.ys, torch.int32, dev), S._const(self.xs, torch.int32, dev)
-        # the origin rows of all windows, padded to whole batches with the last window
-        rows = np.stack([np.repeat(self.ys, nx), np.tile(self.xs, ny)], axis=1).astype(np.int32)
-        self._batches = -(-nWin // B)
-        pad = self._batches * B - nWin
-        self._origins_all = S._const(np.concatenate([rows, np.repeat(rows[-1:], pad, 0)]), torch.int32, dev)
-        self._origins = self._origins_all[:B].clone()
-        md = metadata.detach().float()
+        self.ramp, self.windows = default_ramp(self.overlap), self.ys.size * self.xs.size
+        self._batches = -(-self.windows // self.batch)
+
+    def _metadata(self, md: torch.Tensor) -> torch.Tensor:
+        """One row for the region, or one per window: then ``_md_all`` holds them, padded to whole batches with the last window's."""
+        nWin, B = self.windows, self.batch
         md = md.reshape(1, -1) if md.dim() < 2 else md
         if md.dim() != 2 or md.shape[0] not in (1, nWin):
-            raise ValueError(f"metadata must be (1, F) for the region or ({nWin}, F), one row per window, got {tuple(metadata.shape)}")
-        self._md_all = torch.cat([md, md[-1:].expand(pad, -1)]).contiguous() if md.shape[0] > 1 else None      # one row per window
-        self._md = (md.expand(B, -1) if self._md_all is None else self._md_all[:B]).contiguous().clone()
-        self._ts = temp_series.detach().float().reshape(1, -1).expand(B, -1).contiguous()
-        self._stage = PinnedStage((Hr, Wr), torch.uint8)                                # a host class map travels through pinned memory
-        self.graph, self._out = warm_up_and_capture(self._run, dev, warmup)
+            raise ValueError(f"metadata must be (1, F) for the region or ({nWin}, F), one row per window, got {tuple(md.shape)}")
+        self._md_all = torch.cat([md, md[-1:].expand(self._batches * B - nWin, -1)]).contiguous() if md.shape[0] > 1 else None
+        return (md.expand(B, -1) if self._md_all is None else self._md_all[:B]).contiguous().clone()
 
     def _run(self) -> torch.Tensor:
-        x = _gather(self._region[0], self._dw_t2, *self._region[1:], self._origins, self._norm, self.window, self._ncls, self.dtype,
+        x = _gather(self._tile[0], self._dw_t2, *self._tile[1:], self._origins, self._norm, self.window, self._ncls, self.dtype,
                     pad8(2 * self._ncls + N_CONT))
         return self.model(x, self._ts, self._md)
-
-    def _set_dw_t2(self, dw_t2):
-        if tuple(np.shape(dw_t2)) != self.shape:
-            raise ValueError(f"RegionSession was built for a region of {self.shape}, dw_t2 is {tuple(np.shape(dw_t2))}")
-        if str(dw_t2.dtype) not in ("uint8", "torch.uint8"):
-            raise TypeError(f"dw_t2 must be uint8 class ids, got {dw_t2.dtype}")
-        if isinstance(dw_t2, torch.Tensor) and dw_t2.is_cuda:
-            self._dw_t2.copy_(dw_t2, non_blocking=True)
-        else:
-            self._stage.upload(dw_t2, self._dw_t2)
 
     @torch.no_grad()
     def __call__(self, dw_t2=None) -> RegionResult:
         if dw_t2 is not None:
-            self._set_dw_t2(dw_t2)
+            upload(dw_t2, self._dw_t2, self._stage, "dw_t2")
         B, nWin, T = self.batch, self.windows, self.window
         wo = torch.empty((nWin,) + tuple(self._out.shape[1:]), dtype=torch.float32, device=self._out.device)
         for i in range(self._batches):
             self._origins.copy_(self._origins_all[i * B:(i + 1) * B], non_blocking=True)
             if self._md_all is not None:
                 self._md.copy_(self._md_all[i * B:(i + 1) * B], non_blocking=True)
-            self.graph.replay()
+            self._replay()
             valid = min(B, nWin - i * B)
             wo[i * B:i * B + valid].copy_(self._out[:valid], non_blocking=True)
         out = _stitch(wo, self._ys, self._xs, *self.shape, self.ramp)[None]
-        r = S.result(out, self._temp_orig, self._region[0], self._dw_t2.clone()[None], self._mean, self._std)
+        r = S.result(out, self._temp_orig, self._tile[0], self._dw_t2.clone()[None], self._mean, self._std)
         return RegionResult(out, wo, r.ndvi, r.temp_c, r.delta, r.dw_t2, r.stats)
 
 
@@ -324,30 +295,13 @@ class RegionSession:
 # --------------------------------------------------------------------------- #
 def run_region(checkpoint: str, region: str, palette_json: str, metrics_json: str, window: int = CONFIG.model.img_size,
                overlap: Optional[int] = None, batch: int = 8, precision: str = "fp16", output: str = "", device: str = "cuda") -> dict:
-    """Body of the CLI: one session call on the region of ``region`` (.npz: dw, rgb, ndvi, temp, metadata_raw = (lat, lon,
-    population, year_t1, month_t1, year_t2, month_t2), optionally dw_t2 (the edited class map), temp_series (raw) and temp_orig:
-    ``scenario``'s keys without a canvas).  Returns -- and with ``output`` writes as .npz -- output (1,2,Hr,Wr), ndvi, temp_c,
-    delta (1,Hr,Wr), dw_t2, stats and the statistics by name, and the window grid: ys, xs, window, overlap, ramp."""
-    from .checkpoint import load_model
-    with open(palette_json) as f:
-        palette = S.palette_from_hex(json.load(f))
-    with open(metrics_json) as f:
-        metrics = json.load(f)
-    S._check_metrics(metrics, S.METRIC_KEYS)
-    d = np.load(region)
-    md = S.metadata_row(*[float(v) for v in d["metadata_raw"]], metrics["meta_mean"], metrics["meta_std"])
-    ts = S.normalize_temp_series(d["temp_series"], metrics) if "temp_series" in d else np.zeros((1, 60), dtype=np.float32)
-    dw = np.asarray(d["dw"])
-    dw = dw[0] if dw.ndim == 3 else dw
-    Hr, Wr = dw.shape
-    model = load_model(checkpoint, device=device, spatial_channels=2 * palette.shape[0] + N_CONT, seq_len=ts.shape[1])
-    model.set_precision(precision)
-    dev = lambda a, dt, shape: torch.from_numpy(np.ascontiguousarray(np.reshape(a, shape), dtype=dt)).to(device)       # noqa: E731
-    sess = RegionSession(model, dev(dw, np.uint8, (Hr, Wr)), dev(d["rgb"], np.float32, (3, Hr, Wr)), dev(d["ndvi"], np.float32, (Hr, Wr)),
-                         dev(d["temp"], np.float32, (Hr, Wr)), dev(md, np.float32, md.shape), dev(ts, np.float32, ts.shape), palette=palette,
-                         metrics=metrics, window=window, overlap=overlap, batch=batch,
-                         dw_t2=dev(d["dw_t2"], np.uint8, (Hr, Wr)) if "dw_t2" in d else None,
-                         temp_orig=dev(d["temp_orig"], np.float32, (Hr, Wr)) if "temp_orig" in d else None)
+    """Body of the CLI: one session call on the region of ``region`` (.npz: ``scenario.load_tile``'s keys; dw_t2 is the edited class
+    map).  Returns -- and with ``output`` writes as .npz -- output (1,2,Hr,Wr), ndvi, temp_c, delta (1,Hr,Wr), dw_t2, stats and the
+    statistics by name, and the window grid: ys, xs, window, overlap, ramp."""
+    t = S.load_tile(region, metrics_json, palette_json, device, checkpoint)
+    t.model.set_precision(precision)
+    sess = RegionSession(*t[:7], palette=t.palette, metrics=t.metrics, window=window, overlap=overlap, batch=batch, dw_t2=t.dw_t2,
+                         temp_orig=t.temp_orig)
     r = sess()
     stats = r.stats.cpu().numpy()
     res = {"output": r.output.cpu().numpy(), "ndvi": r.ndvi.cpu().numpy(), "temp_c": r.temp_c.cpu().numpy(), "delta": r.delta.cpu().numpy(),

@@ -22,17 +22,17 @@ tested against, bit for bit.
 from __future__ import annotations
 
 import json
+from collections import namedtuple
 from typing import Optional, Sequence, Tuple
 
 import numpy as np
 import torch
 
 from . import functional as F_
-from ._capture import PinnedStage, freeze, warm_up_and_capture
+from ._capture import PinnedStage
+from ._tile import METRIC_KEYS, N_CONT, TileSession, check_metrics, check_ncls, check_palette, check_tile, const, norm_row, upload
 from .functional import Act, _dev, call, dtype_code, lib, pad8
 
-N_CONT = 5               # rgb (3) + ndvi + temperature
-METRIC_KEYS = ("rgb_mean", "rgb_std", "temp_mean", "temp_std", "meta_mean", "meta_std", "temp_series_mean", "temp_series_std")
 STAT_NAMES = ("mean_delta", "min_delta", "max_delta", "edited_pixels", "mean_delta_edited")
 
 
@@ -59,18 +59,11 @@ def palette_from_hex(colours: Sequence[str]) -> np.ndarray:
     return np.array([[int(c.lstrip("#")[i:i + 2], 16) for i in (0, 2, 4)] for c in colours], dtype=np.uint8)
 
 
-def _palette(palette) -> np.ndarray:
-    p = np.asarray(palette)
-    if p.ndim != 2 or p.shape[1] != 3 or p.dtype != np.uint8 or p.shape[0] < 1:
-        raise ValueError("palette must be an (ncls, 3) uint8 array, ncls >= 1")
-    return np.ascontiguousarray(p)
-
-
 def canvas_to_dw_map_host(canvas: np.ndarray, target_shape: Tuple[int, int], palette, original_map: Optional[np.ndarray] = None) -> np.ndarray:
     """``canvas_to_dw_map`` (:70-110): (Hc, Wc, 4) RGBA -> (H, W) uint8 class map.  The canvas is resized with nearest
     neighbour; a pixel takes the palette entry of smallest RGB distance (the first on a tie -- integer squared distances,
     which order exactly as ``cdist``'s); with ``original_map``, pixels of alpha 0 keep its class."""
-    canvas, palette = np.asarray(canvas), _palette(palette)
+    canvas, palette = np.asarray(canvas), check_palette(palette)
     if canvas.ndim != 3 or canvas.shape[2] != 4:
         raise ValueError(f"canvas must be (Hc, Wc, 4) RGBA, got {canvas.shape}")
     H, W = int(target_shape[0]), int(target_shape[1])
@@ -85,24 +78,10 @@ def canvas_to_dw_map_host(canvas: np.ndarray, target_shape: Tuple[int, int], pal
     return np.where(arr[:, :, 3] > 0, nearest, original_map).astype(np.uint8)
 
 
-def _check_metrics(metrics: dict, keys=METRIC_KEYS[:4]):
-    missing = [k for k in keys if k not in metrics]
-    if missing:
-        raise ValueError(f"metrics lacks {missing} (the keys of normalization_metrics.json)")
-
-
-def _norm_row(metrics: dict) -> np.ndarray:
-    _check_metrics(metrics)
-    row = np.array(list(metrics["rgb_mean"]) + list(metrics["rgb_std"]) + [metrics["temp_mean"], metrics["temp_std"]], dtype=np.float64)
-    if row.shape != (8,):
-        raise ValueError("metrics: rgb_mean and rgb_std hold three values each")
-    return row
-
-
 def normalized_planes_host(rgb, ndvi, temp, metrics: dict) -> np.ndarray:
     """The five continuous planes of the network's input, (5, H, W) fp32: float64 arithmetic rounded to float once (:136-139, :149)."""
-    _check_metrics(metrics)
-    row = _norm_row(metrics)
+    check_metrics(metrics)
+    row = norm_row(metrics)
     colour = np.asarray(rgb, dtype=np.float64)
     h, w = colour.shape[-2:]
     planes = np.empty((N_CONT, h, w), dtype=np.float64)
@@ -115,7 +94,7 @@ def normalized_planes_host(rgb, ndvi, temp, metrics: dict) -> np.ndarray:
 def prepare_input_host(dw_t1, rgb, ndvi, temp, canvas, palette, metrics: dict) -> np.ndarray:
     """The dense input of ``prepare_input`` (:134-149) as a (1, 2 ncls + 5, H, W) fp32 array:
     ``[one-hot dw_t1 | rgb | ndvi | temp | one-hot dw_t2]``, the planes normalised in float64 and rounded to float once."""
-    palette = _palette(palette)
+    palette = check_palette(palette)
     dw_t1 = np.asarray(dw_t1)
     if dw_t1.ndim == 3:
         dw_t1 = dw_t1[0]
@@ -139,7 +118,7 @@ def metadata_row(lat, lon, population, year_t1, month_t1, year_t2, month_t2, met
 
 def normalize_temp_series(ts, metrics: dict) -> np.ndarray:
     """The (1, T) fp32 temperature series of :167-168."""
-    _check_metrics(metrics, ("temp_series_mean", "temp_series_std"))
+    check_metrics(metrics, ("temp_series_mean", "temp_series_std"))
     series = np.asarray(ts, dtype=np.float64).reshape(1, -1)
     return ((series - float(metrics["temp_series_mean"])) / float(metrics["temp_series_std"])).astype(np.float32)
 
@@ -147,27 +126,6 @@ def normalize_temp_series(ts, metrics: dict) -> np.ndarray:
 # --------------------------------------------------------------------------- #
 # the two launches
 # --------------------------------------------------------------------------- #
-def _const(v, dtype, dev) -> torch.Tensor:
-    """A small host array (or device tensor) as a contiguous device tensor."""
-    if isinstance(v, torch.Tensor):
-        return v.to(device=dev, dtype=dtype).contiguous()
-    return torch.from_numpy(np.ascontiguousarray(v)).to(dtype).to(dev)
-
-
-def _tile(dw_t1, rgb, ndvi, temp):
-    """The base tile, checked: dw_t1 (H,W) uint8, rgb (3,H,W), ndvi (H,W) | (1,H,W), temp likewise, fp32, on the device."""
-    dw_t1 = _dev(dw_t1, "dw_t1", torch.uint8)
-    if dw_t1.dim() == 3 and dw_t1.shape[0] == 1:
-        dw_t1 = dw_t1[0]
-    if dw_t1.dim() != 2:
-        raise ValueError(f"dw_t1 must be (H, W), got {tuple(dw_t1.shape)}")
-    H, W = dw_t1.shape
-    rgb = _dev(rgb, "rgb", torch.float32, (3, H, W))
-    ndvi = _dev(ndvi.reshape(H, W) if isinstance(ndvi, torch.Tensor) and ndvi.numel() == H * W else ndvi, "ndvi", torch.float32, (H, W))
-    temp = _dev(temp.reshape(H, W) if isinstance(temp, torch.Tensor) and temp.numel() == H * W else temp, "temp", torch.float32, (H, W))
-    return dw_t1, rgb, ndvi, temp
-
-
 def _canvas4(canvas: torch.Tensor) -> torch.Tensor:
     if canvas.dim() == 3:
         canvas = canvas[None]
@@ -179,15 +137,13 @@ def _canvas4(canvas: torch.Tensor) -> torch.Tensor:
 class _Tables:
     """The device-side constants of ``mau_scenario_pack`` for one (tile shape, canvas shape, palette, metrics)."""
 
-    def __init__(self, tile_shape, canvas_shape, palette, metrics: dict, dev):
-        palette = _palette(palette)
-        self.ncls = palette.shape[0]
-        if self.ncls > lib.mau_scenario_max_classes():
-            raise ValueError(f"mau_scenario_pack takes at most {lib.mau_scenario_max_classes()} classes, the palette has {self.ncls}")
-        self.palette = _const(palette, torch.uint8, dev)
-        self.norm = _const(_norm_row(metrics), torch.float64, dev)
-        self.yidx = _const(nearest_index_table(canvas_shape[0], tile_shape[0]), torch.int32, dev)
-        self.xidx = _const(nearest_index_table(canvas_shape[1], tile_shape[1]), torch.int32, dev)
+    def __init__(self, tile_shape, canvas_shape, palette, metrics: dict, dev, norm: Optional[torch.Tensor] = None):
+        palette = check_palette(palette)
+        self.ncls = check_ncls(palette.shape[0], "mau_scenario_pack")
+        self.palette = const(palette, torch.uint8, dev)
+        self.norm = const(norm_row(metrics), torch.float64, dev) if norm is None else norm      # a session has uploaded its own
+        self.yidx = const(nearest_index_table(canvas_shape[0], tile_shape[0]), torch.int32, dev)
+        self.xidx = const(nearest_index_table(canvas_shape[1], tile_shape[1]), torch.int32, dev)
 
 
 def _pack(dw_t1, rgb, ndvi, temp, canvas, tb: _Tables, dtype: torch.dtype):
@@ -207,7 +163,7 @@ def pack(dw_t1, rgb, ndvi, temp, canvas, palette, metrics: dict, dtype: torch.dt
     dw_t2 (N, H, W) uint8).  dw_t1 (H,W) uint8, rgb (3,H,W) raw 0..255, ndvi (H,W), temp (H,W) raw degrees C, fp32; canvas
     (Hc,Wc,4) or (N,Hc,Wc,4) uint8 RGBA; all on the device.  palette (ncls,3) uint8 and the metrics dict are host values.
     Bit-identical to ``data.pack_tiles`` on the class maps and normalised planes of ``prepare_input_host``."""
-    dw_t1, rgb, ndvi, temp = _tile(dw_t1, rgb, ndvi, temp)
+    dw_t1, rgb, ndvi, temp = check_tile(dw_t1, rgb, ndvi, temp)
     canvas = _canvas4(_dev(canvas, "canvas", torch.uint8))
     tb = _Tables(dw_t1.shape, canvas.shape[1:3], palette, metrics, dw_t1.device)
     return _pack(dw_t1, rgb, ndvi, temp, canvas, tb, dtype)
@@ -260,7 +216,7 @@ def result(output: torch.Tensor, temp_orig: Optional[torch.Tensor], dw_t1: torch
 # --------------------------------------------------------------------------- #
 # the session
 # --------------------------------------------------------------------------- #
-class ScenarioSession:
+class ScenarioSession(TileSession):
     """``ScenarioSession(model, dw_t1, rgb, ndvi, temp, metadata, temp_series, palette=..., metrics=...)(canvas) -> ScenarioResult``.
 
     The base tile (device tensors: dw_t1 (H,W) uint8; rgb (3,H,W), ndvi (H,W), temp (H,W) fp32, raw values), the metadata row
@@ -275,28 +231,16 @@ class ScenarioSession:
     def __init__(self, model: torch.nn.Module, dw_t1, rgb, ndvi, temp, metadata, temp_series, *, palette, metrics: dict,
                  canvas_shape: Tuple[int, int] = (512, 512), scenarios: int = 1, temp_orig=None, warmup: int = 2,
                  clone_output: bool = True):
-        dw_t1, rgb, ndvi, temp = _tile(dw_t1, rgb, ndvi, temp)
-        for t, what in ((metadata, "metadata"), (temp_series, "temp_series")):
-            F_._require_cuda(t, f"ScenarioSession({what})")
         if scenarios < 1:
             raise ValueError("scenarios must be >= 1")
-        _check_metrics(metrics)
-        dev = dw_t1.device
-        N, (Hc, Wc) = int(scenarios), (int(canvas_shape[0]), int(canvas_shape[1]))
-        self.model = model
+        super().__init__(model, dw_t1, rgb, ndvi, temp, metadata, temp_series, metrics, scenarios, temp_orig=temp_orig)
+        N, (Hc, Wc) = self.batch, (int(canvas_shape[0]), int(canvas_shape[1]))
         self.clone_output = clone_output
-        self.dtype = freeze(model)
-        self._tile = tuple(t.detach().clone() for t in (dw_t1, rgb, ndvi, temp))
-        self._temp_orig = self._tile[3] if temp_orig is None else _dev(temp_orig, "temp_orig", torch.float32, tuple(dw_t1.shape)).detach().clone()
-        self._tables = _Tables(dw_t1.shape, (Hc, Wc), palette, metrics, dev)
-        self._mean, self._std = float(metrics["temp_mean"]), float(metrics["temp_std"])
-        self._md = metadata.detach().float().reshape(1, -1).expand(N, -1).contiguous()
-        self._ts = temp_series.detach().float().reshape(1, -1).expand(N, -1).contiguous()
-        self._canvas = torch.zeros((N, Hc, Wc, 4), dtype=torch.uint8, device=dev)
+        self._tables = _Tables(self.shape, (Hc, Wc), palette, metrics, self._device, norm=self._norm)
+        self._canvas = torch.zeros((N, Hc, Wc, 4), dtype=torch.uint8, device=self._device)
         self._stage = PinnedStage((N, Hc, Wc, 4), torch.uint8)                          # host canvases travel through pinned memory
-        # the tickets of the captured reduction are the session's own: a replay never shares them with a launch on another stream
-        self._tickets = torch.zeros(lib.mau_reduce_tickets_elems(), dtype=torch.int32, device=dev)
-        self.graph, self._out = warm_up_and_capture(self._run, dev, warmup)
+        self._tickets = self._own_tickets()
+        self._capture(warmup)
 
     def _run(self) -> ScenarioResult:
         x, dw_t2 = _pack(*self._tile, self._canvas, self._tables, self.dtype)
@@ -309,53 +253,61 @@ class ScenarioSession:
 
     @torch.no_grad()
     def __call__(self, canvas) -> ScenarioResult:
-        if isinstance(canvas, torch.Tensor):
-            src = canvas if canvas.dim() != 3 else canvas[None]
-        else:
-            src = np.asarray(canvas)
-            src = src if src.ndim != 3 else src[None]
-        if tuple(src.shape) != tuple(self._canvas.shape):
-            raise ValueError(f"ScenarioSession was captured for canvases of shape {tuple(self._canvas.shape)} (or one of "
-                             f"{tuple(self._canvas.shape[1:])} when scenarios == 1), got {tuple(np.shape(canvas))}")
-        if str(src.dtype) not in ("uint8", "torch.uint8"):
-            raise TypeError(f"canvas must be uint8 RGBA, got {src.dtype}")
-        if isinstance(src, torch.Tensor) and src.is_cuda:
-            if src.data_ptr() != self._canvas.data_ptr():
-                self._canvas.copy_(src, non_blocking=True)
-        else:
-            self._stage.upload(src, self._canvas)
-        self.graph.replay()
+        src = canvas if isinstance(canvas, torch.Tensor) else np.asarray(canvas)
+        upload(src[None] if src.ndim == 3 else src, self._canvas, self._stage, "canvas")     # (Hc, Wc, 4): the one canvas of scenarios == 1
+        self._replay()
         return self._out.clone() if self.clone_output else self._out
 
 
 # --------------------------------------------------------------------------- #
 # CLI
 # --------------------------------------------------------------------------- #
-def run_tile(checkpoint: str, tile: str, palette_json: str, metrics_json: str, precision: str = "fp16", output: str = "",
-             device: str = "cuda") -> dict:
-    """Body of the CLI: one session call on the tile of ``tile`` (.npz: dw, rgb, ndvi, temp, canvas, metadata_raw = (lat, lon,
-    population, year_t1, month_t1, year_t2, month_t2), optionally temp_series (raw) and temp_orig).  Returns -- and with
-    ``output`` writes as .npz -- ndvi, temp_c, delta, dw_t2, stats and the statistics by name."""
-    from .checkpoint import load_model
-    with open(palette_json) as f:
-        palette = palette_from_hex(json.load(f))
+# what ``load_tile`` read; the first seven fields are the positional arguments of the sessions
+TileInputs = namedtuple("TileInputs", "model dw rgb ndvi temp metadata temp_series dw_t2 temp_orig metrics palette npz")
+
+
+def load_tile(npz_path: str, metrics_json: str, palette_json: Optional[str] = None, device: str = "cuda", checkpoint: Optional[str] = None,
+              ncls: Optional[int] = None) -> TileInputs:
+    """What the command lines of ``scenario``, ``placement`` and ``region`` read.  The .npz holds dw -- (H, W) or (1, H, W) --, rgb,
+    ndvi, temp of H * W values per plane, metadata_raw = (lat, lon, population, year_t1, month_t1, year_t2, month_t2) and optionally
+    temp_series (raw), dw_t2 and temp_orig.  Returns, on ``device``: dw (H, W) uint8; rgb (3, H, W), ndvi, temp (H, W) fp32; metadata
+    (1, 8) (``metadata_row``); temp_series (1, T) (``normalize_temp_series``; zeros (1, 60) without one, :172-175); dw_t2, temp_orig
+    (H, W) or None; then the metrics dict (every key of ``METRIC_KEYS``), the palette (ncls, 3) uint8 of ``palette_json`` (hex
+    colours in class order) or None, and the opened .npz for a tool's own keys (``canvas``).  ``model`` is ``checkpoint``'s for
+    ``ncls`` classes (None: the palette's) -- two one-hot stacks and the five continuous planes -- and series of T, or None."""
+    palette = None
+    if palette_json:
+        with open(palette_json) as f:
+            palette = palette_from_hex(json.load(f))
     with open(metrics_json) as f:
         metrics = json.load(f)
-    _check_metrics(metrics, METRIC_KEYS)
-    d = np.load(tile)
+    check_metrics(metrics, METRIC_KEYS)
+    d = np.load(npz_path)
     md = metadata_row(*[float(v) for v in d["metadata_raw"]], metrics["meta_mean"], metrics["meta_std"])
-    ts = normalize_temp_series(d["temp_series"], metrics) if "temp_series" in d else np.zeros((1, 60), dtype=np.float32)     # (:172-175)
+    ts = normalize_temp_series(d["temp_series"], metrics) if "temp_series" in d else np.zeros((1, 60), dtype=np.float32)
     dw = np.asarray(d["dw"])
     dw = dw[0] if dw.ndim == 3 else dw
     H, W = dw.shape
-    canvas = np.ascontiguousarray(d["canvas"], dtype=np.uint8)
-    model = load_model(checkpoint, device=device, spatial_channels=2 * palette.shape[0] + N_CONT, seq_len=ts.shape[1])
-    model.set_precision(precision)
-    dev = lambda a, dt: torch.from_numpy(np.ascontiguousarray(a, dtype=dt)).to(device)       # noqa: E731
-    sess = ScenarioSession(model, dev(dw, np.uint8), dev(np.reshape(d["rgb"], (3, H, W)), np.float32), dev(np.reshape(d["ndvi"], (H, W)), np.float32),
-                           dev(np.reshape(d["temp"], (H, W)), np.float32), dev(md, np.float32), dev(ts, np.float32), palette=palette,
-                           metrics=metrics, canvas_shape=canvas.shape[-3:-1], scenarios=1 if canvas.ndim == 3 else canvas.shape[0],
-                           temp_orig=dev(np.reshape(d["temp_orig"], (H, W)), np.float32) if "temp_orig" in d else None)
+    model = None
+    if checkpoint:
+        from .checkpoint import load_model
+        model = load_model(checkpoint, device=device, spatial_channels=2 * int(ncls or palette.shape[0]) + N_CONT, seq_len=ts.shape[1])
+    dev = lambda a, dt, shape: torch.from_numpy(np.ascontiguousarray(np.reshape(a, shape), dtype=dt)).to(device)       # noqa: E731
+    optional = lambda key, dt: dev(d[key], dt, (H, W)) if key in d else None                                           # noqa: E731
+    return TileInputs(model, dev(dw, np.uint8, (H, W)), dev(d["rgb"], np.float32, (3, H, W)), dev(d["ndvi"], np.float32, (H, W)),
+                      dev(d["temp"], np.float32, (H, W)), dev(md, np.float32, md.shape), dev(ts, np.float32, ts.shape),
+                      optional("dw_t2", np.uint8), optional("temp_orig", np.float32), metrics, palette, d)
+
+
+def run_tile(checkpoint: str, tile: str, palette_json: str, metrics_json: str, precision: str = "fp16", output: str = "",
+             device: str = "cuda") -> dict:
+    """Body of the CLI: one session call on the tile of ``tile`` (.npz: ``load_tile``'s keys and canvas).  Returns -- and with
+    ``output`` writes as .npz -- ndvi, temp_c, delta, dw_t2, stats and the statistics by name."""
+    t = load_tile(tile, metrics_json, palette_json, device, checkpoint)
+    canvas = np.ascontiguousarray(t.npz["canvas"], dtype=np.uint8)
+    t.model.set_precision(precision)
+    sess = ScenarioSession(*t[:7], palette=t.palette, metrics=t.metrics, canvas_shape=canvas.shape[-3:-1],
+                           scenarios=1 if canvas.ndim == 3 else canvas.shape[0], temp_orig=t.temp_orig)
     r = sess(canvas)
     stats = r.stats.cpu().numpy()
     res = {"ndvi": r.ndvi.cpu().numpy(), "temp_c": r.temp_c.cpu().numpy(), "delta": r.delta.cpu().numpy(), "dw_t2": r.dw_t2.cpu().numpy(),

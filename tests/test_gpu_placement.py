@@ -65,7 +65,8 @@ def test_pack_matches_host_truth_bit_for_bit(mau, pack_case, prec, ld):
     buf = torch.full((n + extra,), float("nan"), dtype=dt, device="cuda")
     before = bits(buf).clone()
     t = [dev(a) for a in (dw, dw2, rgb, ndvi, temp)]
-    norm, edits = dev(mau.scenario._norm_row(METRICS)), dev(EDITS)
+    from mau_amd._tile import norm_row
+    norm, edits = dev(norm_row(METRICS)), dev(EDITS)
     mau._lib.call("mau_placement_pack", *(v.data_ptr() for v in t), edits.data_ptr(), norm.data_ptr(), buf.data_ptr(), ld,
                   mau.functional.dtype_code(dt), B, H, W, PH, PW, NCLS, torch.cuda.current_stream().cuda_stream)
     torch.cuda.synchronize()

@@ -68,7 +68,8 @@ def test_gather_matches_host_truth_bit_for_bit(mau, gather_case, prec, ld):
     buf = torch.full((n + extra,), float("nan"), dtype=dt, device="cuda")
     before = bits(buf).clone()
     t = [dev(a) for a in (dw, dw2, rgb, ndvi, temp)]
-    norm = dev(mau.scenario._norm_row(METRICS))
+    from mau_amd._tile import norm_row
+    norm = dev(norm_row(METRICS))
     mau._lib.call("mau_region_gather", *(v.data_ptr() for v in t), dev(ORIGINS).data_ptr(), norm.data_ptr(), buf.data_ptr(), ld,
                   mau.functional.dtype_code(dt), B, GT, GH, GW, NCLS, torch.cuda.current_stream().cuda_stream)
     torch.cuda.synchronize()

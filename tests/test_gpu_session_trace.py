@@ -31,7 +31,7 @@ GOLDEN = os.path.join(HERE, "golden", "session_trace.json")
 GOLDEN_REPORTS = os.path.join(HERE, "golden", "session_trace_reports")
 TIME_LIMIT = 120.0                                         # seconds for the whole file: a case is a few seconds
 # the modules that bound ``call`` by name and launch in these cases
-CALLERS = ("data", "scenario", "compare", "region", "evaluate", "statistics")
+CALLERS = ("data", "scenario", "placement", "compare", "region", "evaluate", "statistics")
 
 UNET = dict(temporal_embeddings=False, metadata_embeddings=True)
 TRAIN_TILES = [("Alpha Town", 0, (2018, 3), (2020, 4), None, 12), ("Beta", 1, (2019, 1), (2021, 2), None, 9)]
@@ -81,6 +81,27 @@ def scenario_session(mau, work):
         sess = mau.ScenarioSession(net, dw, rgb, ndvi, temp, md, ts, palette=palette, metrics=METRICS, canvas_shape=(64, 80))
         sess(c1)
         sess(c2)
+        torch.cuda.synchronize()
+    return rows
+
+
+def placement_session(mau, work):
+    """48 x 48, 9 classes, stamps of 16 in batches of two, captured (``precision`` given) and eager; each: construct (the baseline
+    replay included), a sweep of three placements -- one class over three origins: the last batch is ragged -- and a second call by
+    stride, four placements in two whole batches."""
+    net = small_net(mau, "unet")
+    rng = np.random.default_rng(52)
+    tile = tuple(dev(a) for a in make_tile(rng, 48, 48))
+    roi = dev((rng.random((48, 48)) < 0.3).astype(np.uint8))
+    g = torch.Generator().manual_seed(6)
+    ts, md = torch.randn(1, 12, generator=g).cuda(), torch.randn(1, 8, generator=g).cuda()
+    with recording(mau) as rows:
+        for graph in (True, False):
+            sess = mau.PlacementSession(net, *tile, md, ts, metrics=METRICS, ncls=9, patch=16, batch=2, roi=roi,
+                                        precision="fp16" if graph else None, graph=graph)
+            assert (sess.graph is not None) == graph and sess.dtype == torch.float16
+            assert sess([1], origins=([0, 32, 16], [0])).rows.shape == (3, 12)
+            assert sess([6], stride=32).rows.shape == (4, 12)
         torch.cuda.synchronize()
     return rows
 
@@ -141,7 +162,8 @@ def eval_drivers(mau, work):
     return rows
 
 
-CASES = {"graphed_inference": graphed_inference, "scenario_session": scenario_session, "comparison_session": comparison_session,
+CASES = {"graphed_inference": graphed_inference, "scenario_session": scenario_session, "placement_session": placement_session,
+         "comparison_session": comparison_session,
          "region_session": region_session, "eval_drivers": eval_drivers}
 
 
