@@ -671,6 +671,64 @@ int mau_placement_result(const float* out, const float* base, const int* edits, 
                          double temp_std, double* rows, double* ws, unsigned* tickets, int B, int H, int W, int ph, int pw,
                          mau_stream_t stream);
 
+/* ---- placement screening: every candidate stamp ranked from ONE input gradient.  The network's input is one-hot: a stamp changes
+ *      exactly two channels of a pixel by +-1, so its first-order effect on a scalar objective is a plain sum of input-gradient
+ *      entries over the stamp's rectangle, with no step size to choose.  ONE launch each, no allocation, no float atomics, graph-
+ *      capturable.  Additive to ABI 5 ----
+ * Definitions.
+ *   Linearisation point: the resident tile with its second class map dw_t2, as mau_placement_pack writes it with every row cls = -1.
+ *   Objective k, 0 <= k < K: row k of objs (K,2) int32 ON THE DEVICE, (ch_k, roi index or -1).  ch_k is 1 for temperature in degrees
+ *     C or 0 for NDVI; the roi index names a plane of rois (R,H,W) uint8, nonzero = inside, -1 = the whole tile.  J_k is the mean
+ *     over roi_k of the forecast: out1 * temp_std + temp_mean for temperature, out0 for NDVI; n_k is the roi's pixel count.
+ *   Seed: dout[k, ch_k, p] = seed_scale * [p in roi_k], the other channel 0.  seed_scale is a positive power of two (default 1) that
+ *     a float holds as a normal number: it moves fp16 gradients away from overflow or underflow and is undone exactly below.
+ *   Gradient: G (K,H,W,ld) in `dtype`, the gradient of sum_k <dout_k, out_k> with respect to the packed input of K copies of the tile.
+ *   Swap term of pixel p towards class c, cur(p) = dw_t2[p]:  s_k(p, c) = G[k,p,off+c] - (cur(p) < ncls ? G[k,p,off+cur(p)] : 0),
+ *     formed in fp64 from the loaded values; off = ncls + 5 is the channel offset of the second one-hot block (mau_placement_pack).
+ *   Coefficient: coef_k = (ch_k == 1 ? temp_std : 1) / (seed_scale * n_k) in fp64 (one product, one division), applied once, after
+ *     the sum.
+ * Every index made from a table value (y0, x0, cls, ch, the roi index) is range-checked in 64-bit before it is used.
+ *
+ * mau_screen_seed: objs, rois (may be NULL when no row names a plane) -> dout (K,2,H,W) fp32, EVERY element written, and counts (K)
+ * fp64 holding the integers n_k (integer-valued additions: the same bits in any order).  A row whose ch is neither 0 nor 1 seeds
+ * nothing; a roi index outside [-1, R), or >= 0 with rois == NULL, is an empty roi (n_k = 0).  One workgroup per objective.
+ * MAU_ERR_ARG: a NULL required pointer, K outside [1, 65535], R < 0, H * W > 2^30, seed_scale no such power of two. */
+int mau_screen_row_elems(void);
+int mau_screen_seed(const int* objs, const unsigned char* rois, int R, double seed_scale, float* dout, double* counts, int K, int H, int W,
+                    mau_stream_t stream);
+/* mau_screen_rows: G with its pixel stride ld >= 2 ncls + 5 (elements) and dtype; dw_t2 (H,W) uint8 (required: the map the
+ * linearisation point was packed with); edits (P,3) int32 ON THE DEVICE, rows of (y0, x0, cls) as mau_placement_pack reads them;
+ * counts and objs as above ->
+ *   rows (K, P, mau_screen_row_elems() = 4) fp64:
+ *     [0] pixels of the stamp inside the tile
+ *     [1] of those, pixels whose class changes (cur(p) != cls)
+ *     [2] predicted change of J_k = coef_k * sum over the stamp's pixels inside the tile of s_k(p, cls)
+ *     [3] non-finite gradient values read for this row: per pixel, G[k,p,off+cls], and G[k,p,off+cur(p)] when cur(p) < ncls.
+ *   The stamp test is mau_placement_pack's: 64-bit, every int32 legal, a stamp over an edge is clipped.  cls outside [0, ncls) gives
+ *   ([0], 0, +0.0, 0) and reads no gradient (the pack would leave the tile as it is).  n_k == 0: [2] is NaN, whatever cls is.  A
+ *   non-finite value propagates into [2] and is counted in [3].
+ * One 256-thread workgroup per (row, objective).  Slot i of the UNCLIPPED ph x pw rectangle, row-major, belongs to thread i % 256; a
+ * thread joins its slots in increasing i and a slot outside the tile contributes nothing (it is skipped, not added as 0), so the order
+ * does not depend on clipping; then the 64 lanes by an xor butterfly 32..1 and the four waves in wave order.  4-byte / 2-byte gathers,
+ * two per pixel, any alignment of G.  A row's bits depend on nothing but its own table row, its objective and the tile -- not on P, on
+ * the row's place in the table, or on K -- and repeat.  Any ph * pw works: the loop visits only the rectangle's rows and columns
+ * inside the tile.
+ * MAU_ERR_ARG: a NULL required pointer, ph or pw < 1, H * W > 2^30, ncls outside [1, mau_scenario_max_classes()], ld < 2 ncls + 5,
+ * K outside [1, 65535], P < 1, a bad dtype or seed_scale. */
+int mau_screen_rows(const void* G, int ld, int dtype, const unsigned char* dw_t2, const int* edits, const double* counts, const int* objs,
+                    double temp_std, double seed_scale, double* rows, int K, int P, int H, int W, int ph, int pw, int ncls,
+                    mau_stream_t stream);
+/* mau_screen_maps: for ONE objective k of the K in G, maps (ncls,H,W) fp32 with maps[c, p] = fl32(coef_k * s_k(p, c)) for every class c
+ * -- "what would this pixel do as class c"; NaN everywhere when n_k == 0.  Every element is written.  Pixel-owned: one thread per
+ * pixel reads the groups of 8 channels that hold the second one-hot block (at most three).  Two load forms, chosen by the host from ld
+ * and the alignment of G alone:
+ *   ld % 8 == 0 and G 16-byte aligned: 16-byte loads (one per group for bf16 / fp16, two for fp32);
+ *   otherwise: element by element, the same groups of 8 from channel (off & ~7) on, no channel at or beyond off + ncls.
+ * The two forms load the same values and compute the same bits.
+ * MAU_ERR_ARG: as mau_screen_rows, and k outside [0, K). */
+int mau_screen_maps(const void* G, int ld, int dtype, const unsigned char* dw_t2, const double* counts, const int* objs, double temp_std,
+                    double seed_scale, float* maps, int k, int K, int H, int W, int ncls, mau_stream_t stream);
+
 /* ---- model comparison: M heads' outputs of ONE tile against one target (the developer app's Model Comparison page,
  *      app_dev/pages/1_Model_Comparison.py with app_dev/app_src/utils.py:170-271), ONE launch each.  Additive to ABI 5 ----
  * mau_compare_result: out (M,2,H,W) fp32 NCHW, the M heads' outputs (channel 0 NDVI, channel 1 normalised temperature);

@@ -17,10 +17,11 @@ from . import data                      # noqa: F401  (input pipeline: compact t
 
 # The tools are also command lines (``python -m mau_amd.evaluate`` ...): they are imported on first use, so that running one as a
 # script does not find it in sys.modules already.
-_LAZY_MODULES = ("sensitivity", "ground_truth", "evaluate", "scenario", "dataset_metrics", "compare", "dataset_build", "region", "statistics", "climate", "rank_tests", "placement")
+_LAZY_MODULES = ("sensitivity", "ground_truth", "evaluate", "scenario", "dataset_metrics", "compare", "dataset_build", "region", "statistics", "climate", "rank_tests", "placement", "screening")
 _LAZY_CLASSES = {"ScenarioSession": "scenario", "ScenarioResult": "scenario", "ComparisonSession": "compare", "ComparisonResult": "compare",
                  "RegionSession": "region", "RegionResult": "region", "ClimateQuery": "climate",
-                 "PlacementSession": "placement", "PlacementResult": "placement"}
+                 "PlacementSession": "placement", "PlacementResult": "placement",
+                 "ScreeningSession": "screening", "ScreeningResult": "screening"}
 
 
 def __getattr__(name):

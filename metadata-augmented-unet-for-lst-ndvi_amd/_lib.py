@@ -144,6 +144,10 @@ PROTOTYPES = {
     "mau_placement_chunks": (_i, [_i, _i]),
     "mau_placement_ws_elems": (_sz, [_i, _i, _i]),
     "mau_placement_result": (_i, [_p, _p, _p, _p, _d, _d, _p, _p, _p, _i, _i, _i, _i, _i, _p]),
+    "mau_screen_row_elems": (_i, []),
+    "mau_screen_seed": (_i, [_p, _p, _i, _d, _p, _p, _i, _i, _i, _p]),
+    "mau_screen_rows": (_i, [_p, _i, _i, _p, _p, _p, _p, _d, _d, _p, _i, _i, _i, _i, _i, _i, _i, _p]),
+    "mau_screen_maps": (_i, [_p, _i, _i, _p, _p, _p, _d, _d, _p, _i, _i, _i, _i, _i, _p]),
     "mau_compare_row_elems": (_i, []),
     "mau_compare_chunks": (_i, [_i, _i]),
     "mau_compare_ws_elems": (_sz, [_i, _i, _i]),

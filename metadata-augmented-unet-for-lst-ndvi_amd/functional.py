@@ -231,8 +231,9 @@ class PackGroup:
             if not (self.fresh_after_step == _GENERATION[0] and st["key"] is not None and st["key"][1] == key[1] and len(self._state) == 1):
                 call("mau_conv3x3_pack_weights_multi", st["table"].data_ptr(), len(self.params), st["tiles"], code, _stream())
             st["key"] = key
-            for w, f, d in zip(self.params, st["wf"], st["wd"]):
-                w._mau_pack = [(key[0], w._version, w.data_ptr(), code), f, d]
+        # (also when nothing was re-packed: after a run in another type the parameters' entries name THAT type's packs)
+        for w, f, d in zip(self.params, st["wf"], st["wd"]):
+            w._mau_pack = [(key[0], w._version, w.data_ptr(), code), f, d]
         return st
 
 
@@ -487,8 +488,9 @@ def _head_param_grads(hslab, C, Co, wshape, stream):
     return red[:, :C].reshape(wshape).contiguous(), red[:, pad8(C)].contiguous()
 
 
-def _head_bwd(a, C, w2, out, dout, tanh0, wshape, stream):
-    """Backward of the head on a materialised activation -> (da, dW, db)."""
+def _head_bwd(a, C, w2, out, dout, tanh0, wshape, stream, params=True):
+    """Backward of the head on a materialised activation -> (da, dW, db); ``params=False``: no head parameter takes a gradient, the
+    slab is not summed and dW, db are None."""
     N, H, W, _ = a.shape
     Co = w2.shape[0]
     dout = dout.contiguous().float()
@@ -496,7 +498,7 @@ def _head_bwd(a, C, w2, out, dout, tanh0, wshape, stream):
     hslab = _head_slab(N, H * W, C, Co, a.device)
     call("mau_head_bwd", a.data_ptr(), _ld(a), w2.data_ptr(), out.data_ptr(), dout.data_ptr(), da.data_ptr(), pad8(C), hslab.data_ptr(), tanh0,
          dtype_code(a.dtype), N, H * W, C, Co, stream)
-    return (da, *_head_param_grads(hslab, C, Co, wshape, stream))
+    return (da, *(_head_param_grads(hslab, C, Co, wshape, stream) if params else (None, None)))
 
 
 # ---- ConvBNReLU.forward, stage by stage ----
@@ -717,7 +719,8 @@ def _dz_fused_head(g: _Geom, st: BNState, ctx, sv, da, dpl):
     call("mau_head_bn_bwd_reduce", sv.y.data_ptr(), g.ldy, *cptrs, sv.w2.data_ptr(), sv.out.data_ptr(), dout.data_ptr(), slab.data_ptr(),
          g.Cout, hslab.data_ptr(), tanh0, g.code, g.N, g.H * g.W, g.Cout, Co, g.stream)
     sums, count, g32 = _finish_sums(g, st, slab)
-    dhw, dhb = _head_param_grads(hslab, g.Cout, Co, hshape, g.stream)
+    # (the slab is a by-product of the reduce pass; its sum is launched only when a head parameter takes a gradient)
+    dhw, dhb = _head_param_grads(hslab, g.Cout, Co, hshape, g.stream) if (ctx.needs_input_grad[10] or ctx.needs_input_grad[11]) else (None, None)
     call("mau_head_bn_bwd_apply", sv.y.data_ptr(), g.ldy, *cptrs, sums.data_ptr(), count, sv.w2.data_ptr(), sv.out.data_ptr(),
          dout.data_ptr(), dy.data_ptr(), g.ldy, tanh0, g.code, g.N, g.H * g.W, g.Cout, Co, g.stream)
     return dy, g32, dhw, dhb
@@ -744,7 +747,7 @@ def _dz_generic(g: _Geom, st: BNState, ctx, sv, da, dpl, apply=True):
     if ctx.head is not None:
         # unfused head: da, dW, db from the saved activation
         _, tanh0, hshape, _ = ctx.head
-        da, dhw, dhb = _head_bwd(sv.a, g.Cout, sv.w2, sv.out, da, tanh0, hshape, stream)
+        da, dhw, dhb = _head_bwd(sv.a, g.Cout, sv.w2, sv.out, da, tanh0, hshape, stream, ctx.needs_input_grad[10] or ctx.needs_input_grad[11])
     elif ctx.up is not None:
         # the upsample's adjoint produces da (its forward read y through BatchNorm + ReLU, or the activation)
         da = _resize_bwd(_as_nhwc(da), 0, g.Cout, (g.H, g.W), stream)

@@ -16,7 +16,7 @@ is the forecast with the stamp minus the forecast of the unedited tile.  It is t
 
 The host twins (pure numpy) are the product's reference; the order-exact twin of the reduction lives with the tests.
 
-    python -m mau_amd.placement CHECKPOINT --tile tile.npz --metrics-json M --classes 1,6 [--patch 32 --stride 16 --batch 8 --roi roi.npy --output out.npz]
+    python -m mau_amd.placement CHECKPOINT --tile tile.npz --metrics-json M --classes 1,6 [--patch 32 --stride 16 --batch 8 --roi roi.npy --screen 8 --output out.npz]
 """
 from __future__ import annotations
 
@@ -81,6 +81,36 @@ def _edit_rows(edits) -> np.ndarray:
     if e.min() < -2 ** 31 or e.max() > 2 ** 31 - 1:
         raise ValueError("edits must fit int32")
     return e.astype(np.int64)
+
+
+def build_edits(shape, patch, ncls: int, classes=None, stride=None, origins=None, edits=None):
+    """The table a session call sweeps, ``(edits (K, 3) int32, classes, ys, xs)``: ``classes`` x the stamp grid of both axes at
+    ``stride`` (an int or (sy, sx); None = the patch) or x ``origins=(ys, xs)``, in ``edits_table``'s order -- or an explicit
+    ``edits`` table, any int32 rows of ``(y0, x0, cls)`` (then classes, ys, xs are None)."""
+    (H, W), (ph, pw) = shape, _patch(patch)
+    if edits is not None:
+        if classes is not None or stride is not None or origins is not None:
+            raise ValueError("give an explicit table of edits or classes with a stride or origins, not both")
+        return _edit_rows(edits).astype(np.int32), None, None, None
+    c = np.asarray([] if classes is None else classes).reshape(-1)
+    if c.size < 1 or not np.issubdtype(c.dtype, np.integer) or c.min() < 0 or c.max() >= ncls:
+        raise ValueError(f"classes must be integers in [0, {ncls}), got {classes!r}")
+
+    def axis(v, n: int, p: int, what: str) -> np.ndarray:
+        v = np.asarray(v).reshape(-1)
+        if v.size < 1 or not np.issubdtype(v.dtype, np.integer) or v.min() < 0 or v.max() > n - p:
+            raise ValueError(f"{what} must be integer origins in [0, {n - p}] (stamps inside the tile)")
+        return v.astype(np.int32)
+
+    if origins is not None:
+        if stride is not None:
+            raise ValueError("give a stride or the origins, not both")
+        ys, xs = axis(origins[0], H, ph, "origins[0]"), axis(origins[1], W, pw, "origins[1]")
+    else:
+        sy, sx = (ph, pw) if stride is None else _patch(stride)
+        ys, xs = stamp_grid(H, ph, sy), stamp_grid(W, pw, sx)
+    c = c.astype(np.int32)
+    return edits_table(ys, xs, c), c, ys, xs
 
 
 def stamp_mask(edit, shape: Tuple[int, int], patch) -> np.ndarray:
@@ -231,6 +261,8 @@ class PlacementResult:
 
     def grid(self, cls: int, entry: int = 1) -> np.ndarray:
         """(ny, nx): entry ``entry`` of the rows of class ``cls``, by stamp origin."""
+        if self.classes is None:
+            raise ValueError("an explicit table of edits has no grid")
         at = np.flatnonzero(self.classes == int(cls))
         if at.size == 0:
             raise ValueError(f"class {cls} was not swept (classes: {self.classes.tolist()})")
@@ -306,30 +338,12 @@ class PlacementSession(TileSession):
         """The network's output (2, H, W) fp32 for the unedited tile."""
         return self._base
 
-    def _classes(self, classes) -> np.ndarray:
-        c = np.asarray(classes).reshape(-1)
-        if c.size < 1 or not np.issubdtype(c.dtype, np.integer) or c.min() < 0 or c.max() >= self.ncls:
-            raise ValueError(f"classes must be integers in [0, {self.ncls}), got {classes!r}")
-        return c.astype(np.int32)
-
-    def _axis(self, v, n: int, p: int, what: str) -> np.ndarray:
-        v = np.asarray(v).reshape(-1)
-        if v.size < 1 or not np.issubdtype(v.dtype, np.integer) or v.min() < 0 or v.max() > n - p:
-            raise ValueError(f"{what} must be integer origins in [0, {n - p}] (stamps inside the tile)")
-        return v.astype(np.int32)
-
     @torch.no_grad()
-    def __call__(self, classes, stride=None, origins=None) -> PlacementResult:
-        (H, W), (ph, pw), B = self.shape, self.patch, self.batch
-        classes = self._classes(classes)
-        if origins is not None:
-            if stride is not None:
-                raise ValueError("give a stride or the origins, not both")
-            ys, xs = self._axis(origins[0], H, ph, "origins[0]"), self._axis(origins[1], W, pw, "origins[1]")
-        else:
-            sy, sx = (ph, pw) if stride is None else _patch(stride)
-            ys, xs = stamp_grid(H, ph, sy), stamp_grid(W, pw, sx)
-        edits = edits_table(ys, xs, classes)
+    def __call__(self, classes=None, stride=None, origins=None, edits=None) -> PlacementResult:
+        """``edits``: an explicit (K, 3) table of ``(y0, x0, cls)`` rows instead of ``classes`` x a grid -- the rows a screening
+        picked; the result then has no grid (``classes``, ``ys``, ``xs`` are None)."""
+        B = self.batch
+        edits, classes, ys, xs = build_edits(self.shape, self.patch, self.ncls, classes, stride, origins, edits)
         K = edits.shape[0]
         table = torch.empty((K, ROW), dtype=torch.float64, device=self._base.device)
         for k0 in range(0, K, B):
@@ -351,13 +365,44 @@ def _int_list(text: str) -> Sequence[int]:
 
 
 def run_tile(checkpoint: str, tile: str, metrics_json: str, classes="1,6", patch: int = 32, stride: Optional[int] = None, batch: int = 8,
-             roi: str = "", ncls: int = 9, precision: str = "fp16", output: str = "", device: str = "cuda") -> dict:
+             roi: str = "", ncls: int = 9, precision: str = "fp16", output: str = "", device: str = "cuda", screen: int = 0) -> dict:
     """Body of the CLI: one sweep on the tile of ``tile`` (.npz: ``scenario.load_tile``'s keys; temp_orig is not used); ``roi``: a
     .npy (H, W) mask.  Returns -- and with ``output`` writes as .npz -- rows, edits, classes, ys, xs, ``grid_c<cls>_e<entry>`` per
-    class for entries 1, 4 and 7, and the unedited forecast ndvi, temp_c."""
+    class for entries 1, 4 and 7, and the unedited forecast ndvi, temp_c.
+
+    ``screen = N > 0``: the whole grid is screened from one input gradient (``screening.ScreeningSession``, the objective
+    "temperature over the roi, else the tile") and only the N candidates per class with the most negative predicted change are swept
+    exactly.  The result then holds ``edits`` (all candidates), ``predicted`` (their (P, 4) screening rows), ``pred_grid_c<cls>``,
+    ``screened_index`` / ``screened_edits`` (class-major, best first), ``screened_rows`` (their exact (n, 12) rows), ``best`` (per
+    class, the screened candidate with the lowest exact mean dT over the roi, else the tile) and ``spearman``: the rank correlation of
+    the predicted change with that exact figure over the swept subset."""
     t = S.load_tile(tile, metrics_json, device=device, checkpoint=checkpoint, ncls=ncls)
     cls = _int_list(classes) if isinstance(classes, str) else list(classes)
     mask = torch.from_numpy((np.load(roi) != 0).astype(np.uint8).reshape(tuple(t.dw.shape))).to(device) if roi else None
+    if int(screen) < 0:
+        raise ValueError(f"--screen takes a number of candidates per class, got {screen}")
+    if screen:
+        from . import screening
+        scr = screening.ScreeningSession(*t[:7], metrics=t.metrics, ncls=ncls, patch=patch, objectives=(("temp", mask),), dw_t2=t.dw_t2,
+                                         precision=precision)
+        p = scr(cls, stride=stride)
+        pick = np.concatenate([p.top_index(screen, 0, c) for c in p.classes])
+        sess = PlacementSession(*t[:7], metrics=t.metrics, ncls=ncls, patch=patch, batch=batch, dw_t2=t.dw_t2, roi=mask, precision=precision)
+        r = sess(edits=p.edits[pick])
+        exact = r.rows[:, 7 if roi else 1]
+        res = {"edits": p.edits, "classes": p.classes, "ys": p.ys, "xs": p.xs, "ndvi": r.ndvi, "temp_c": r.temp_c, "predicted": p.rows[0],
+               "screened_index": pick, "screened_edits": r.edits, "screened_rows": r.rows,
+               "spearman": np.float64(screening.spearman(p.rows[0, pick, 2], exact)),
+               **{f"pred_grid_c{c}": p.grid(c) for c in p.classes}}
+        best = []
+        for c in p.classes:
+            at = np.flatnonzero(r.edits[:, 2] == c)
+            k = at[np.nanargmin(exact[at])] if at.size and not np.isnan(exact[at]).all() else None
+            best.append([np.nan] * 3 if k is None else [r.edits[k, 0], r.edits[k, 1], exact[k]])
+        res["best"] = np.array(best, dtype=np.float64)
+        if output:
+            np.savez(output, **res)
+        return res
     sess = PlacementSession(*t[:7], metrics=t.metrics, ncls=ncls, patch=patch, batch=batch, dw_t2=t.dw_t2, roi=mask, precision=precision)
     r = sess(cls, stride=stride)
     res = {"rows": r.rows, "edits": r.edits, "classes": r.classes, "ys": r.ys, "xs": r.xs, "ndvi": r.ndvi, "temp_c": r.temp_c,
@@ -379,14 +424,26 @@ def _cli():
              classes: str = typer.Option("1,6", help="land-cover classes to place, comma separated"),
              patch: int = 32, stride: int = typer.Option(-1, help="pixels between stamp origins; -1 = the patch"), batch: int = 8,
              roi: str = typer.Option("", help=".npy (H, W) mask of a region of interest"), ncls: int = 9, precision: str = "fp16",
-             output: str = "", device: str = "gpu"):
+             output: str = "", device: str = "gpu",
+             screen: int = typer.Option(0, help="N > 0: screen the grid from one input gradient, sweep only the N best candidates per class")):
         """Where on a tile does a block of one land-cover class change the forecast temperature most?"""
         dev = F_.typer_device(device)
         try:
-            res = run_tile(checkpoint, tile, metrics_json, classes, patch, None if stride < 0 else stride, batch, roi, ncls, precision, output, dev)
+            res = run_tile(checkpoint, tile, metrics_json, classes, patch, None if stride < 0 else stride, batch, roi, ncls, precision, output, dev,
+                           screen)
         except ValueError as e:
             raise typer.BadParameter(str(e))
         ny, nx = len(res["ys"]), len(res["xs"])
+        if screen:
+            n = res["screened_rows"].shape[0]
+            typer.echo(f"tile {res['ndvi'].shape[0]} x {res['ndvi'].shape[1]}: {len(res['classes'])} classes x {ny} x {nx} stamps of {patch} screened "
+                       f"from one gradient, {n} swept exactly in {-(-n // batch)} batches of {batch}")
+            typer.echo(f"Spearman rank correlation of predicted and exact change over the {n} swept: {float(res['spearman']):.4f}")
+            for c, (y0, x0, v) in zip(res["classes"], res["best"]):
+                typer.echo(f"class {int(c)}: lowest exact mean_dt{'_roi' if roi else ''} among the screened {v:.6g} at (y0, x0) = ({int(y0)}, {int(x0)})")
+            if output:
+                typer.echo(f"Saved placement result to {output}")
+            return
         K = res["rows"].shape[0]
         typer.echo(f"tile {res['ndvi'].shape[0]} x {res['ndvi'].shape[1]}: {len(res['classes'])} classes x {ny} x {nx} stamps of {patch}, "
                    f"{-(-K // batch)} batches of {batch}")
